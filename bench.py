@@ -104,8 +104,50 @@ def parse(argv=None):
     ap.add_argument('--no-cpu-pin', action='store_true', help='leave the host threads to the scheduler instead of pinning them to cores near the GPU')
     ap.add_argument('--no-pin', action='store_true', help='do not restrict every rank to its own GPU through HIP_VISIBLE_DEVICES')
     ap.add_argument('--debug-allocs', action='store_true', help='print the Python stacks of device allocations (hipMalloc) made inside the timed region')
-    ap.add_argument('--report-dir', default=os.path.join(ROOT, 'gpurun_out', 'bench_ranks'), help='where every rank writes rank_<r>.json')
-    return ap.parse_args(argv)
+    ap.add_argument('--report-dir', default=None,
+                    help='where every rank writes rank_<r>.json (default: a new directory in the system temp dir for every launch, shared by its '
+                         'ranks; the checkout itself may be read-only)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed repeats, write what the last one returned for its last frame (the label image a caller of '
+                         'Tracker.run_sequence receives) as DIR/<name>.npy in float32: same arguments, same inputs, so two builds compare '
+                         'output for output (rank 0, single-sequence mode only)')
+    args = ap.parse_args(argv)
+    if args.dump_outputs and args.sequences > 0:
+        ap.error('--dump-outputs needs the single-sequence mode (no --sequences)')
+    return args
+
+
+def default_report_dir():
+    """A fresh directory for the rank reports of one launch.  Ranks started by bench.py itself get theirs from self_launch; ranks started by
+    an outside launcher have no common parent and agree on a name keyed by user and rendezvous (every rank rewrites its own rank_<r>.json
+    before any rank reads it, and only ranks 0 .. world-1 are read, so files of an earlier launch under the same name are never used)."""
+    import tempfile
+    if 'WORLD_SIZE' not in os.environ:
+        return tempfile.mkdtemp(prefix='frtm_bench_ranks_')
+    launch = '%s_%s' % (os.environ.get('TORCHELASTIC_RUN_ID', 'run'), os.environ.get('MASTER_PORT', 'port'))
+    return os.path.join(tempfile.gettempdir(), 'frtm_bench_ranks_%d_%s' % (os.getuid(), launch))
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """arrays: name -> tensor.  Each is written as out_dir/<name>.npy in float32; all of them together stay under DUMP_MAX_BYTES (a larger
+    array is replaced by a fixed, seeded sample of its elements, written with the flat indices of the sample as <name>_index.npy)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    budget = DUMP_MAX_BYTES // max(len(arrays), 1) // 2
+    files = []
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy().astype(np.float32).reshape(t.shape)
+        if a.nbytes > budget:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=budget // 8, replace=False))
+            np.save(os.path.join(out_dir, name + '_index.npy'), idx.astype(np.float64))
+            files.append(name + '_index.npy')
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+        files.append(name + '.npy')
+    return files
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -128,6 +170,8 @@ def self_launch(args):
     env.setdefault('OMP_NUM_THREADS', '8')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', str(args.gpus),
            '--master-addr', '127.0.0.1', '--master-port', str(_free_port()), os.path.abspath(__file__)] + sys.argv[1:]
+    if args.report_dir is None:                 # one new directory for the ranks of this launch
+        cmd += ['--report-dir', default_report_dir()]
     return subprocess.call(cmd, env=env)
 
 
@@ -769,6 +813,8 @@ def main():
     args = parse()
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         sys.exit(self_launch(args))
+    if args.report_dir is None:
+        args.report_dir = default_report_dir()
     rank = int(os.environ.get('RANK', 0))
     world = int(os.environ.get('WORLD_SIZE', 1))
     local = int(os.environ.get('LOCAL_RANK', 0))
@@ -973,6 +1019,13 @@ def main():
                          exec_flops=list(ext.pass_exec_flops), form_flops=list(ext.pass_form_flops), aug=list(aug_log),
                          enqueue_ms=1e3 * getattr(tracker, 'last_enqueue_seconds', 0.0)))
         _phase('timed repeat %d: %.1f frames/s' % (rep, n_total / T))
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # the LAST repeat (its sequence is fixed by the arguments; which repeat is the median depends on the clock), its last frame
+        dumped = dict(dir=os.path.abspath(args.dump_outputs), repeat=len(runs) - 1, frame=len(runs[-1]['outputs']) - 1,
+                      sequence_seed=1 + rank + 1000 * (len(runs) - 1), target_model_seed=4242 + rank)
+        dumped['files'] = dump_outputs(args.dump_outputs, {'labels_last_step': runs[-1]['outputs'][-1]})
+        _phase('outputs of repeat %(repeat)d, frame %(frame)d (sequence seed %(sequence_seed)d) written to %(dir)s' % dumped)
     # the line reports the MEDIAN repeat (by wall time; every rank holds the same max-reduced times, so every rank picks the same one)
     order = sorted(range(len(runs)), key=lambda i: runs[i]['T'])
     med = runs[order[len(order) // 2]]
@@ -1128,6 +1181,8 @@ def main():
         'stream_placement': __import__('frtm_vos_amd.model.tracker', fromlist=['STREAM_PROBE']).STREAM_PROBE,
         'valid': bool(ok.item() > 0),
     }
+    if dumped is not None:
+        out['dump_outputs'] = dumped           # which repeat / frame the files hold, so that two builds compare the same step
     if world > 1:
         # the group that carried barrier + max-reduce: 'nccl' (= RCCL) or, when RCCL did not come up on every rank with one visible device each, 'gloo'
         out['dist_backend_used'] = dist_used

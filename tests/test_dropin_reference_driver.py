@@ -1,137 +1,148 @@
 """The upstream driver really drops onto the package (north_star: "the reference evaluate.py drops onto it unchanged").
 
-BUILD CONTAINER ONLY: the upstream ``evaluate.py`` is imported from /root/reference where it lies (never copied; the test is skipped when
-the reference is absent, e.g. on the GPU box).  INTEGRATION.md section A's aliasing is applied -- the package's module tree under the
-upstream names ``model`` / ``lib`` -- plus a stand-in for ``easydict`` (absent in this image), the upstream file is executed, and its own
-``Parameters`` / ``get_model()`` are driven: every class it imported must be the package's, its hyper-parameters must arrive in the package's
-``Discriminator``, and ``load_state_dict`` must accept exactly the upstream ``refiner.*`` checkpoint keys (taken from the UPSTREAM
-``SegNetwork``'s own state dict).  No GPU here: the extractor's upload to the device is stubbed, nothing is computed.
+Fixture G18 (oracle/make_golden_dropin.py) records, from the upstream ``evaluate.py`` run under INTEGRATION.md section A's aliasing (the
+package's module tree under the upstream names ``model`` / ``lib``): the names it imports, the call shape of its ``Parameters.get_model()``
+(callee, number of positional arguments, keyword names of every call, in evaluation order), the hyper-parameters of its ``Parameters`` for
+a ResNet-18 and a ResNet-101 checkpoint (full and fast schedule), and the layout of the UPSTREAM ``SegNetwork``'s state dict (``refiner.*``
+checkpoint keys, shapes, dtypes).  Here the aliasing is applied again: every recorded import must resolve to the package's object,
+upstream's ``get_model()`` is replayed on the package's classes in exactly the recorded call shape and must build the package's
+``Tracker`` from an upstream-shaped checkpoint, the upstream hyper-parameters must arrive in the package's ``Discriminator``, and
+``load_state_dict`` must accept exactly the upstream keys.  No GPU here: the extractor's upload to the device is stubbed, nothing is computed.
 """
 import importlib
-import importlib.util
-import os
+import inspect
+import json
 import sys
-import types
 
 import pytest
 import torch
-
-REF = '/root/reference'
-pytestmark = pytest.mark.skipif(not os.path.isfile(os.path.join(REF, 'evaluate.py')), reason='upstream reference not present (build container only)')
 
 PKG_MODEL = ('tracker', 'discriminator', 'optimizer', 'memory', 'feature_extractor', 'seg_network', 'augmenter')
 PKG_LIB = ('tensorlist', 'utils', 'image', 'datasets', 'evaluation')
 
 
-class _EasyDict(dict):
-    """Stand-in for easydict.EasyDict (absent here): attribute access, nested dicts converted."""
-
-    def __init__(self, d=None, **kw):
-        super().__init__()
-        for k, v in dict(d or {}, **kw).items():
-            self[k] = v
-
-    def __setitem__(self, k, v):
-        super().__setitem__(k, _EasyDict(v) if isinstance(v, dict) and not isinstance(v, _EasyDict) else v)
-
-    __setattr__ = __setitem__
-
-    def __getattr__(self, k):
-        try:
-            return self[k]
-        except KeyError:
-            raise AttributeError(k)
+@pytest.fixture
+def g18(golden):
+    z = golden('g18_dropin')
+    return {k: json.loads(str(z[k])) for k in z.files}
 
 
 @pytest.fixture
-def upstream_evaluate(monkeypatch):
-    """INTEGRATION.md section A, then the upstream file executed as a module."""
+def aliased():
+    """the package's module tree under the upstream names."""
     import frtm_vos_amd  # noqa: F401
-    saved = {k: v for k, v in sys.modules.items() if k in ('model', 'lib', 'easydict') or k.startswith(('model.', 'lib.'))}
+    saved = {k: v for k, v in sys.modules.items() if k in ('model', 'lib') or k.startswith(('model.', 'lib.'))}
     for k in saved:
         del sys.modules[k]
-    ed = types.ModuleType('easydict')
-    ed.EasyDict = _EasyDict
-    sys.modules['easydict'] = ed
     sys.modules['model'] = importlib.import_module('frtm_vos_amd.model')
     sys.modules['lib'] = importlib.import_module('frtm_vos_amd.lib')
     for m in PKG_MODEL:
         sys.modules['model.' + m] = importlib.import_module('frtm_vos_amd.model.' + m)
     for m in PKG_LIB:
         sys.modules['lib.' + m] = importlib.import_module('frtm_vos_amd.lib.' + m)
-    spec = importlib.util.spec_from_file_location('upstream_evaluate', os.path.join(REF, 'evaluate.py'))
-    mod = importlib.util.module_from_spec(spec)
-    old_flag, sys.dont_write_bytecode = sys.dont_write_bytecode, True
-    path0 = list(sys.path)
     try:
-        spec.loader.exec_module(mod)             # runs the imports and the class definition; the __main__ block does not run
-        yield mod
+        yield
     finally:
-        sys.dont_write_bytecode = old_flag
-        sys.path[:] = path0
-        for k in [k for k in sys.modules if k in ('model', 'lib', 'easydict') or k.startswith(('model.', 'lib.'))]:
+        for k in [k for k in sys.modules if k in ('model', 'lib') or k.startswith(('model.', 'lib.'))]:
             del sys.modules[k]
         sys.modules.update(saved)
 
 
-def _upstream_refiner_state(in_channels):
-    """State dict of the UPSTREAM SegNetwork (model/seg_network.py, pure torch: importable here), as 'refiner.*' checkpoint keys."""
-    spec = importlib.util.spec_from_file_location('upstream_seg_network', os.path.join(REF, 'model', 'seg_network.py'))
-    mod = importlib.util.module_from_spec(spec)
-    lib = types.ModuleType('lib')
-    lib_utils = types.ModuleType('lib.utils')
-    ref_utils = importlib.util.spec_from_file_location('upstream_lib_utils', os.path.join(REF, 'lib', 'utils.py'))
-    um = importlib.util.module_from_spec(ref_utils)
-    hold = {k: sys.modules.get(k) for k in ('lib', 'lib.utils')}
-    try:
-        ref_utils.loader.exec_module(um)
-        lib_utils.__dict__.update({k: v for k, v in um.__dict__.items() if not k.startswith('__')})
-        lib.utils = lib_utils
-        sys.modules['lib'], sys.modules['lib.utils'] = lib, lib_utils
-        spec.loader.exec_module(mod)
-    finally:
-        for k, v in hold.items():
-            if v is None:
-                sys.modules.pop(k, None)
-            else:
-                sys.modules[k] = v
-    from collections import OrderedDict
-    chans = OrderedDict(layer5=in_channels * 2, layer4=in_channels, layer3=in_channels // 2, layer2=in_channels // 4)
-    torch.manual_seed(5)
-    net = mod.SegNetwork(1, 64, chans, True)
-    return {'refiner.' + k: v.clone() for k, v in net.state_dict().items()}
+def _upstream_refiner_state(g18):
+    """An upstream-shaped checkpoint: the UPSTREAM SegNetwork's 'refiner.*' keys, shapes and dtypes (G18), seeded values."""
+    gen = torch.Generator().manual_seed(5)
+    out = {}
+    for k, shape, dtype in g18['refiner_state']:
+        dt = getattr(torch, dtype)
+        out[k] = torch.randn(shape, generator=gen).to(dt) if dt.is_floating_point else torch.randint(0, 9, shape, generator=gen).to(dt)
+    return out
 
 
-def test_upstream_evaluate_drops_onto_the_package(upstream_evaluate, monkeypatch):
-    ev = upstream_evaluate
+def _upstream_case(g18, in_channels, fast):
+    return next(c for c in g18['params']['cases'] if c['in_channels'] == in_channels and c['fast'] == fast)
+
+
+def _plain(v):
+    if isinstance(v, dict):
+        return {k: _plain(x) for k, x in v.items()}
+    if isinstance(v, (list, tuple)):
+        return [_plain(x) for x in v]
+    return v
+
+
+def test_upstream_evaluate_drops_onto_the_package(g18, aliased, monkeypatch):
+    from frtm_vos_amd.evaluate import Parameters
     from frtm_vos_amd.model import augmenter, discriminator, feature_extractor, seg_network, tracker
     from frtm_vos_amd.lib import datasets, evaluation
-    # (1) everything the upstream driver imported (evaluate.py:18-23) is the package's
-    assert ev.Tracker is tracker.Tracker
-    assert ev.ResnetFeatureExtractor is feature_extractor.ResnetFeatureExtractor
-    assert ev.SegNetwork is seg_network.SegNetwork
-    assert ev.ImageAugmenter is augmenter.ImageAugmenter
-    assert ev.DAVISDataset is datasets.DAVISDataset and ev.YouTubeVOSDataset is datasets.YouTubeVOSDataset
-    assert ev.evaluate_dataset is evaluation.evaluate_dataset
-    assert ev.Parameters.__module__ == 'upstream_evaluate'                 # ... while Parameters is upstream's own code
-    # (2) upstream Parameters on an upstream-shaped checkpoint (ResNet-18 variant: autodetected from the refiner's layer4 reduce conv, :38-44)
-    weights = _upstream_refiner_state(256)
+    # (1) every name the upstream driver imports (evaluate.py:18-23) resolves, under the aliasing, to the package's object
+    got = {name: getattr(importlib.import_module(module), name) for module, name in g18['imports']}
+    assert len(got) == len(g18['imports']) == 7
+    assert got['Tracker'] is tracker.Tracker
+    assert got['ResnetFeatureExtractor'] is feature_extractor.ResnetFeatureExtractor
+    assert got['SegNetwork'] is seg_network.SegNetwork
+    assert got['ImageAugmenter'] is augmenter.ImageAugmenter
+    assert got['DAVISDataset'] is datasets.DAVISDataset and got['YouTubeVOSDataset'] is datasets.YouTubeVOSDataset
+    assert got['evaluate_dataset'] is evaluation.evaluate_dataset
+    # (2) an upstream-shaped checkpoint (ResNet-18 variant: autodetected from the refiner's layer4 reduce conv, :38-44), read like upstream reads it
+    weights = _upstream_refiner_state(g18)
     assert weights['refiner.TSE.layer4.reduce.0.weight'].shape[1] == 256
-    p = ev.Parameters(weights, device='cpu')
-    assert p.feature_extractor == 'resnet18' and p.init_iters == (5, 10, 10, 10, 10) and p.update_iters == (10,)
-    assert ev.Parameters(weights, fast=True, device='cpu').init_iters == (5, 10, 10, 10)
-    # (3) get_model() (evaluate.py:91-105) builds the package's Tracker; no GPU here: the extractor's device upload is stubbed
-    if not torch.cuda.is_available():
+    up = _upstream_case(g18, 256, False)
+    assert up['feature_extractor'] == 'resnet18' and up['init_iters'] == [5, 10, 10, 10, 10] and up['update_iters'] == [10]
+    assert _upstream_case(g18, 256, True)['init_iters'] == [5, 10, 10, 10]
+    p = Parameters(weights, device='cpu')
+    assert p.feature_extractor == up['feature_extractor'] and list(p.init_iters) == up['init_iters'] and list(p.update_iters) == up['update_iters']
+    assert list(Parameters(weights, fast=True, device='cpu').init_iters) == _upstream_case(g18, 256, True)['init_iters']
+    # (3) upstream's get_model() (evaluate.py:91-105) replayed on the package's classes in its recorded call shape (G18 get_model_calls):
+    # every constructor call goes to the class the upstream name resolves to, with exactly the recorded number of positional arguments and
+    # keyword names, so that a keyword the package made required or a changed positional order fails here.  The values are the upstream
+    # hyper-parameters (equal to the package's Parameters: test_upstream_parameters_match_the_packages_own_driver).
+    dev = 'cuda:0' if torch.cuda.is_available() else 'cpu'
+    if dev == 'cpu':                                                           # no GPU here: the extractor's device upload is stubbed
         monkeypatch.setattr(feature_extractor.ResnetFeatureExtractor, 'to', lambda self, device: self)
-    else:
-        p = ev.Parameters(weights, device='cuda:0')
-    mdl = p.get_model()
+    p = Parameters(weights, device=dev)
+    calls = g18['get_model_calls']
+    shape = {name: (npos, kws) for kind, name, npos, kws in calls if kind == 'class'}
+    assert list(shape) == ['ImageAugmenter', 'ResnetFeatureExtractor', 'SegNetwork', 'Tracker']          # construction order
+    assert [kind for kind, *_ in calls].count('class') == len(shape)                                     # each class built once
+
+    def make(name, *args):
+        npos, kws = shape[name]
+        assert len(args) == npos and kws == [], (name, npos, kws)             # upstream's positional arguments, no keywords
+        return got[name](*args)
+
+    aug = make('ImageAugmenter', p.aug_params)
+    ext = make('ResnetFeatureExtractor', p.feature_extractor).to(dev)
+    p.disc_params.in_channels = ext.get_out_channels()[p.disc_params.layer]
+    outs = ext.get_out_channels()
+    chans = {L: n for L, n in outs.items() if L in p.refnet_params.layers}
+    refiner = make('SegNetwork', p.disc_params.out_channels, p.refnet_params.nchannels, chans, p.refnet_params.use_batch_norm)
+    mdl = make('Tracker', aug, ext, p.disc_params, refiner, dev)
+    mdl.load_state_dict(weights)
+    mdl.to(dev)
+
+    def accepts(obj, method, npos, kws):
+        m = getattr(obj, method, None)
+        if not callable(m):
+            return False
+        try:
+            inspect.signature(m).bind(*([None] * npos), **{k: None for k in kws})
+        except TypeError:
+            return False
+        except ValueError:                                                     # (a builtin without a signature)
+            return True
+        return True
+    for kind, name, npos, kws in calls:                # every method call upstream makes is accepted, in its recorded shape, by the replay's objects
+        if kind == 'method':
+            assert any(accepts(o, name, npos, kws) for o in (ext, outs, mdl)), (name, npos, kws)
     assert type(mdl) is tracker.Tracker and type(mdl.refiner) is seg_network.SegNetwork
     assert type(mdl.feature_extractor) is feature_extractor.ResnetFeatureExtractor and mdl.feature_extractor.name == 'resnet18'
     assert p.disc_params.in_channels == 256                                    # read back from get_out_channels() (:95)
     for k, v in weights.items():                                               # the checkpoint really arrived in the refiner
         assert torch.equal(mdl.state_dict()[k].cpu(), v), k
     assert set(mdl.state_dict().keys()) == set(weights.keys())                 # "exactly the refiner.* keys" 
+    own = Parameters(weights, device=dev).get_model()                          # the package's own driver builds the same model
+    assert type(own) is tracker.Tracker and own.state_dict().keys() == mdl.state_dict().keys()
+    assert all(torch.equal(own.state_dict()[k].cpu(), v) for k, v in weights.items())
     # (4) the upstream hyper-parameters arrive in the package's Discriminator through TargetObject(disc_params=...) (tracker.py:21-22)
     t = tracker.TargetObject(obj_id=1, disc_params=mdl.disc_params, index=1, start_frame=0, start_mask=None)
     d = t.discriminator
@@ -150,16 +161,20 @@ def test_upstream_evaluate_drops_onto_the_package(upstream_evaluate, monkeypatch
         mdl.load_state_dict(dict(weights, **{'feature_extractor.conv1.weight': torch.zeros(1)}))
 
 
-def test_upstream_parameters_match_the_packages_own_driver(upstream_evaluate):
-    """The package's evaluate.Parameters (its own driver) carries the same hyper-parameters as upstream's (evaluate.py:32-34,46-89)."""
+def test_upstream_parameters_match_the_packages_own_driver(g18):
+    """The package's evaluate.Parameters (its own driver) carries the same hyper-parameters as upstream's (evaluate.py:32-34,46-89), for both
+    checkpoint widths and both schedules, and refuses a width upstream refuses."""
     from frtm_vos_amd.evaluate import Parameters as Own
-    w = {'refiner.TSE.layer4.reduce.0.weight': torch.zeros(64, 1024, 1, 1)}
-    for fast in (False, True):
-        up, own = upstream_evaluate.Parameters(w, fast=fast, device='cpu'), Own(w, fast=fast, device='cpu')
-        assert up.feature_extractor == own.feature_extractor == 'resnet101'
-        assert dict(up.disc_params) == {k: v for k, v in dict(own.disc_params).items() if k in up.disc_params}
-        assert dict(up.refnet_params) == dict(own.refnet_params)
-
-        def plain(d):
-            return {k: (plain(v) if isinstance(v, dict) else v) for k, v in d.items()}
-        assert plain(up.aug_params) == plain(own.aug_params)
+    assert [c['feature_extractor'] for c in g18['params']['cases'] if c['in_channels'] == 1024] == ['resnet101', 'resnet101']
+    for up in g18['params']['cases']:
+        own = Own({'refiner.TSE.layer4.reduce.0.weight': torch.zeros(64, up['in_channels'], 1, 1)}, fast=up['fast'], device='cpu')
+        assert own.feature_extractor == up['feature_extractor']
+        assert list(own.init_iters) == up['init_iters'] and list(own.update_iters) == up['update_iters']
+        assert (own.num_aug, own.train_skipping, own.learning_rate) == (up['num_aug'], up['train_skipping'], up['learning_rate'])
+        assert set(up['disc_params']) <= set(own.disc_params)
+        assert up['disc_params'] == {k: v for k, v in _plain(dict(own.disc_params)).items() if k in up['disc_params']}
+        assert up['refnet_params'] == _plain(own.refnet_params)
+        assert up['aug_params'] == _plain(own.aug_params)
+    assert g18['params']['unknown_width_512_raises'] == 'ValueError'
+    with pytest.raises(ValueError):
+        Own({'refiner.TSE.layer4.reduce.0.weight': torch.zeros(64, 512, 1, 1)}, device='cpu')

@@ -144,10 +144,10 @@ def test_one_tracker_serves_sequences_with_different_object_counts_under_graph_r
         assert any(int((x[-1] == o).sum()) > 10 for o in s.obj_ids)       # objects are tracked to the end (non-degenerate masks)
 
 
-def test_bench_starts_two_ranks_and_reports_the_update_work():
+def test_bench_starts_two_ranks_and_reports_the_update_work(tmp_path):
     """`python bench.py --gpus 2` launches two ranks itself (gloo + --share-gpu: both on cuda:0), each tracks its own
     sequence, rank 0 prints one line with n_gpus = 2 and the counters of the per-frame update work."""
-    rep = os.path.join(ROOT, 'gpurun_out', 'bench_ranks_test')
+    rep = str(tmp_path / 'ranks')
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--dist-backend', 'gloo', '--share-gpu',
                           '--steps', '18', '--warmup', '2', '--backbone', 'resnet18', '--size', '240x432', '--report-dir', rep],
                          stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)

@@ -329,7 +329,7 @@ def test_many_refiners_with_parallel_graph_branches_in_one_process():
     assert r.returncode == 0 and 'DONE 200' in r.stdout, (r.returncode, r.stdout[-500:], r.stderr[-1500:])
 
 
-def test_bench_sharded_mode_two_ranks_on_the_gpu():
+def test_bench_sharded_mode_two_ranks_on_the_gpu(tmp_path):
     """`python bench.py --gpus 2 --sequences 5` (strong scaling: ONE dataset cut over the ranks) with two real ranks sharing cuda:0 over gloo:
     the ranks take disjoint shares that cover the 5 sequences, rank 0 reports sum of frames / max wall time, and the update work of every
     sequence ran (counters summed over the shard).  The N = 1 value of the same dataset is within a few percent of frames / seconds of
@@ -338,7 +338,7 @@ def test_bench_sharded_mode_two_ranks_on_the_gpu():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    rep = os.path.join(root, 'gpurun_out', 'bench_shard_test')
+    rep = str(tmp_path / 'ranks')
     base = [sys.executable, os.path.join(root, 'bench.py'), '--dist-backend', 'gloo', '--share-gpu', '--sequences', '5', '--steps', '12', '--warmup', '2',
             '--backbone', 'resnet18', '--fast', '--size', '240x432', '--report-dir', rep, '--no-cpu-baseline']
     out = subprocess.run(base + ['--gpus', '2'], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
