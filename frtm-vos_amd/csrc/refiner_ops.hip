@@ -400,6 +400,181 @@ __global__ __launch_bounds__(256, 4) void k_project_tail(const float* __restrict
 }
 
 // ------------------------------------------------------------------------------------------
+// Bicubic resampling of the Upsampler head (model/seg_network.py: Upsampler), F.interpolate(x, (H, W), mode='bicubic',
+// align_corners=False) as documented:
+//   scale = in / out per axis (a size is given, not a scale factor); source coordinate s = (dst + 0.5) * scale - 0.5, NOT clamped
+//   at 0 for the cubic mode; four taps at floor(s) - 1 .. floor(s) + 2 with their indices clamped into the map; cubic convolution
+//   with A = -0.75 at t = s - floor(s): weights k2(t + 1), k1(t), k1(1 - t), k2(2 - t) with
+//   k1(x) = ((A + 2) x - (A + 3)) x^2 + 1   (|x| <= 1)  and  k2(x) = ((A x - 5A) x + 8A) x - 4A   (1 < |x| < 2).
+// Both kernels below apply it separably, horizontal taps first, then vertical, with the same expressions: the fused tail's z patch
+// equals the unfused resize up to the compiler's contraction choices.
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ int bc_taps(int d, float scale, float wt[4]) {
+  const float A = -0.75f;
+  const float s = __fsub_rn(__fmul_rn(scale, (float)d + 0.5f), 0.5f);
+  const float f = floorf(s), t = s - f;
+  const float x0 = t + 1.f, x3 = 2.f - t, x2 = 1.f - t;
+  wt[0] = ((A * x0 - 5.f * A) * x0 + 8.f * A) * x0 - 4.f * A;
+  wt[1] = ((A + 2.f) * t - (A + 3.f)) * t * t + 1.f;
+  wt[2] = ((A + 2.f) * x2 - (A + 3.f)) * x2 * x2 + 1.f;
+  wt[3] = ((A * x3 - 5.f * A) * x3 + 8.f * A) * x3 - 4.f * A;
+  return (int)f - 1;                                         // first tap (unclamped)
+}
+__device__ __forceinline__ float bc_dot(const float wt[4], float a, float b, float c, float d) {
+  return wt[0] * a + wt[1] * b + wt[2] * c + wt[3] * d;
+}
+
+// out[pl] = bicubic(in[pl], (h,w) -> (H,W)), any ratio up or down.  One thread per output pixel computes the taps once and walks
+// `planes_per_z` planes (coalesced along x in the output), like k_bilinear_resize.  The unfused fallback of the Upsampler head.
+__global__ __launch_bounds__(256) void k_bicubic_resize(const float* __restrict__ in, int h, int w, float* __restrict__ out, int H, int W,
+                                                         int planes, int planes_per_z) {
+  const int pix = blockIdx.x * 256 + threadIdx.x;
+  if (pix >= H * W) return;
+  const int y = pix / W, x = pix - y * W;
+  float wy[4], wx[4];
+  const int r0 = bc_taps(y, (float)h / (float)H, wy), c0 = bc_taps(x, (float)w / (float)W, wx);
+  int ro[4], co[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    ro[k] = min(max(r0 + k, 0), h - 1) * w;
+    co[k] = min(max(c0 + k, 0), w - 1);
+  }
+  const int p0 = blockIdx.y * planes_per_z, p1 = min(planes, p0 + planes_per_z);
+  const size_t hw = (size_t)h * w, HW = (size_t)H * W;
+  for (int pl = p0; pl < p1; ++pl) {
+    const float* p = in + pl * hw;
+    float hx[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) hx[k] = bc_dot(wx, p[ro[k] + co[0]], p[ro[k] + co[1]], p[ro[k] + co[2]], p[ro[k] + co[3]]);
+    out[pl * HW + pix] = bc_dot(wy, hx[0], hx[1], hx[2], hx[3]);
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// Tail of the Upsampler head: out = conv2(interpolate(y, (Ho, Wo), bicubic)) for the single output channel, as ONE kernel (the
+// model is k_project_tail).  Every workgroup rebuilds in LDS the patch of the resized map that its 16x64 output tile and the conv
+// halo read, BT_CG channels per round, straight from y; the full-resolution C-channel tensor never reaches HBM:
+//   A  y patch (BT_YR x BT_YC source pixels, indices clamped into the map)      -> ybuf
+//   B  horizontal cubic taps of the 66 z columns                                -> hb   (BT_YR x 66)
+//   C  vertical cubic taps of the 18 z rows, zero outside the image (conv2 pad) -> zb   (18 x 66)
+//   D  3x3 x 1-channel conv, 4 output rows per thread, accumulated over the channels in registers
+// The source rows / columns a tile reads span floor(17 * scale) + 4 / floor(65 * scale) + 4 pixels, so the fixed patch bounds the
+// ratio: upscale >= ~1.6x vertically and >= ~1.9x horizontally, any larger (480p / 720p / 1080p frames: ~4x from the 2x layer2 map).
+// LDS 35 KB per workgroup: 4 workgroups (16 waves) per CU.
+// ------------------------------------------------------------------------------------------
+#define BT_TH 16
+#define BT_TW 64
+#define BT_ZR (BT_TH + 2)
+#define BT_ZC (BT_TW + 2)
+#define BT_YR 16
+#define BT_YC 40
+#define BT_CG 3
+#define BT_BRG 3                                              // stage B: 3 row groups x 66 columns = 198 threads
+#define BT_CCG 14                                             // stage C: 18 rows x 14 column groups = 252 threads
+
+__global__ __launch_bounds__(256) void k_project_tail_bicubic(const float* __restrict__ y, int C, int h, int w, const float* __restrict__ wgt,
+                                                               const float* __restrict__ bias, float* __restrict__ out, int Ho, int Wo) {
+  constexpr int NY = BT_YR * BT_YC, NYL = (BT_CG * NY + 255) / 256;         // y patch elements per thread
+  __shared__ float ybuf[BT_CG][BT_YR][BT_YC];
+  __shared__ float hb[BT_CG][BT_YR][BT_ZC + 1];
+  __shared__ float zb[BT_CG][BT_ZR][BT_ZC + 1];
+  const int tid = threadIdx.x, n = blockIdx.z;
+  const int Y0 = blockIdx.y * BT_TH, X0 = blockIdx.x * BT_TW;
+  const float sy = (float)h / (float)Ho, sx = (float)w / (float)Wo;
+  float wt[4];
+  // patch origin = first tap of the first z row / column inside the image (the taps only grow along the tile)
+  const int yr0 = bc_taps(max(Y0 - 1, 0), sy, wt), yc0 = bc_taps(max(X0 - 1, 0), sx, wt);
+  // A: element e = tid + k*256 of the [BT_CG][BT_YR][BT_YC] patch -> offset inside one channel plane, -1 past the patch
+  int a_goff[NYL], a_chan[NYL];
+#pragma unroll
+  for (int k = 0; k < NYL; ++k) {
+    const int e = tid + k * 256;
+    const int g = e / NY, r = (e - g * NY) / BT_YC, cc = e - g * NY - r * BT_YC;
+    a_chan[k] = e < BT_CG * NY ? g : -1;
+    a_goff[k] = min(max(yr0 + r, 0), h - 1) * w + min(max(yc0 + cc, 0), w - 1);
+  }
+  // B: thread (b_rg, b_j) forms z column b_j of the patch rows b_rg, b_rg + 3, ...: that column's taps stay in registers
+  const int b_rg = tid / BT_ZC, b_j = tid - b_rg * BT_ZC;
+  const bool b_on = tid < BT_BRG * BT_ZC;
+  float b_w[4];
+  const int zx = X0 - 1 + b_j;
+  const int b_c = min(max(bc_taps(min(max(zx, 0), Wo - 1), sx, b_w) - yc0, 0), BT_YC - 4);
+  // C: thread (c_i, c_jg) forms z row c_i at the columns c_jg, c_jg + 14, ...; rows / columns outside the image are conv2's zeros
+  const int c_i = min(tid / BT_CCG, BT_ZR - 1), c_jg = tid - (tid / BT_CCG) * BT_CCG;
+  const bool c_on = tid < BT_ZR * BT_CCG;
+  const int zy = Y0 - 1 + c_i;
+  float c_w[4];
+  const int c_r = min(max(bc_taps(min(max(zy, 0), Ho - 1), sy, c_w) - yr0, 0), BT_YR - 4);
+  const bool c_row = zy >= 0 && zy < Ho;
+  const int tx = tid & 63, ty = tid >> 6;
+  float acc[4] = {0.f, 0.f, 0.f, 0.f};
+  const float* yn = y + (size_t)n * C * h * w;
+  const size_t hw = (size_t)h * w;
+  float pre[NYL];
+  auto fetch = [&](int c0) {
+#pragma unroll
+    for (int k = 0; k < NYL; ++k) pre[k] = (a_chan[k] >= 0 && c0 + a_chan[k] < C) ? yn[(size_t)(c0 + a_chan[k]) * hw + a_goff[k]] : 0.f;
+  };
+  fetch(0);
+  for (int c0 = 0; c0 < C; c0 += BT_CG) {
+    const int ncg = min(BT_CG, C - c0);
+    // A: registers -> ybuf, then start the next group's loads
+#pragma unroll
+    for (int k = 0; k < NYL; ++k) if (a_chan[k] >= 0) (&ybuf[0][0][0])[tid + k * 256] = pre[k];
+    __syncthreads();
+    if (c0 + BT_CG < C) fetch(c0 + BT_CG);
+    // B: horizontal taps
+    if (b_on) {
+#pragma unroll
+      for (int g = 0; g < BT_CG; ++g)
+#pragma unroll
+        for (int m = 0; m < (BT_YR + BT_BRG - 1) / BT_BRG; ++m) {
+          const int r = b_rg + BT_BRG * m;
+          if (r < BT_YR) {
+            const float* v = &ybuf[g][r][b_c];
+            hb[g][r][b_j] = bc_dot(b_w, v[0], v[1], v[2], v[3]);
+          }
+        }
+    }
+    __syncthreads();
+    // C: vertical taps
+    if (c_on) {
+#pragma unroll
+      for (int g = 0; g < BT_CG; ++g)
+#pragma unroll
+        for (int m = 0; m < (BT_ZC + BT_CCG - 1) / BT_CCG; ++m) {
+          const int j = c_jg + BT_CCG * m;
+          if (j < BT_ZC) {
+            const bool in = c_row && X0 - 1 + j >= 0 && X0 - 1 + j < Wo;
+            zb[g][c_i][j] = in ? bc_dot(c_w, hb[g][c_r][j], hb[g][c_r + 1][j], hb[g][c_r + 2][j], hb[g][c_r + 3][j]) : 0.f;
+          }
+        }
+    }
+    __syncthreads();
+    // D: 3x3 conv, output rows ty*4 .. ty*4+3 at column tx
+    for (int g = 0; g < ncg; ++g) {
+      const float* f = wgt + (c0 + g) * 9;
+      float zz[6][3];
+#pragma unroll
+      for (int r = 0; r < 6; ++r)
+#pragma unroll
+        for (int d = 0; d < 3; ++d) zz[r][d] = zb[g][ty * 4 + r][tx + d];
+#pragma unroll
+      for (int o = 0; o < 4; ++o)
+#pragma unroll
+        for (int k = 0; k < 9; ++k) acc[o] += zz[o + k / 3][k % 3] * f[k];
+    }
+    // next round: ybuf is rewritten after B's barrier above; hb after the next A barrier; zb after two more barriers
+  }
+  const float b = bias ? bias[0] : 0.f;
+#pragma unroll
+  for (int o = 0; o < 4; ++o) {
+    const int yy = Y0 + ty * 4 + o, xx = X0 + tx;
+    if (yy < Ho && xx < Wo) out[((size_t)n * Ho + yy) * Wo + xx] = acc[o] + b;
+  }
+}
+
+// ------------------------------------------------------------------------------------------
 // conv2 (3x3, C -> 1) after two resampling steps is linear in y, and the channel sum commutes with the resampling:
 //   conv2(R(U(y)))(p) = sum_t sum_c w[c][t] R(U(y_c))(p + t) = sum_t R(U(Y_t))(p + t),     Y_t = sum_c w[c][t] y_c   (t = one of the nine taps)
 // so the tail only has to resample NINE maps instead of C = 32 (round 5; k_project_tail then runs on Y with one-hot weights).  This kernel forms
@@ -500,6 +675,32 @@ int frtm_project_tail(const float* y, int n, int C, int h, int w, const float* w
                  "frtm_project_tail: resize ratio %.3f x %.3f outside the fused kernel's patch (use pyrup2x + bilinear_resize + filter_scores)", sy, sx);
   dim3 g(ceil_div(Wo, PT_TW), ceil_div(Ho, PT_TH), n);
   k_project_tail<<<g, 256, 0, (hipStream_t)stream>>>(y, C, h, w, w3x3, bias, out, Ho, Wo);
+  FRTM_LAUNCH_CHECK();
+  return FRTM_OK;
+}
+
+int frtm_bicubic_resize(const float* in, int planes, int h, int w, float* out, int H, int W, frtm_stream_t stream) {
+  FRTM_CHECK_ARG(in && out && planes > 0 && h > 0 && w > 0 && H > 0 && W > 0, "frtm_bicubic_resize: bad argument");
+  FRTM_CHECK_ARG((size_t)H * W < 0x7fffffff && (size_t)h * w < 0x7fffffff, "frtm_bicubic_resize: map too large");
+  const int ppz = 8;
+  dim3 g(ceil_div(H * W, 256), ceil_div(planes, ppz));
+  k_bicubic_resize<<<g, 256, 0, (hipStream_t)stream>>>(in, h, w, out, H, W, planes, ppz);
+  FRTM_LAUNCH_CHECK();
+  return FRTM_OK;
+}
+
+int frtm_project_tail_bicubic(const float* y, int n, int C, int h, int w, const float* w3x3, const float* bias, int Ho, int Wo, float* out,
+                              frtm_stream_t stream) {
+  FRTM_CHECK_ARG(y && w3x3 && out && n > 0 && C > 0 && h > 0 && w > 0 && Ho > 0 && Wo > 0, "frtm_project_tail_bicubic: bad argument");
+  // LDS patch bounds: the source rows / columns an 18 x 66 z patch (16x64 output tile + conv halo) reads through the cubic taps
+  // (one row / column of margin for the rounding of the source coordinates)
+  const double sy = (double)h / Ho, sx = (double)w / Wo;
+  FRTM_CHECK_ARG((int)((BT_ZR - 1) * sy) + 6 <= BT_YR && (int)((BT_ZC - 1) * sx) + 6 <= BT_YC,
+                 "frtm_project_tail_bicubic: resize ratio %.3f x %.3f outside the fused kernel's patch (use bicubic_resize + filter_scores)",
+                 sy, sx);
+  dim3 g(ceil_div(Wo, BT_TW), ceil_div(Ho, BT_TH), n);
+  FRTM_CHECK_ARG(n <= 65535, "frtm_project_tail_bicubic: at most 65535 samples per call");
+  k_project_tail_bicubic<<<g, 256, 0, (hipStream_t)stream>>>(y, C, h, w, w3x3, bias, out, Ho, Wo);
   FRTM_LAUNCH_CHECK();
   return FRTM_OK;
 }

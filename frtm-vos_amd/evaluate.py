@@ -21,8 +21,10 @@ class AttrDict(dict):
 class Parameters:
 
     def __init__(self, weights=None, fast=False, device='cuda:0', feature_extractor=None, backbone_weights=None, feature_batch=16, trunk_lanes=2,
-                 ytvos_fork_solver=False, refiner_graphs=None, aug_fill='telea'):
+                 ytvos_fork_solver=False, refiner_graphs=None, aug_fill='telea', upsampler='compat'):
         self.device = device
+        self.upsampler = upsampler                # refiner head: 'compat' (BackwardCompatibleUpsampler, the reference's default) or 'bicubic'
+        #                                           (Upsampler, the head of the YouTube-VOS fork); both load the same checkpoint keys
         self.aug_fill = aug_fill                  # first-frame hole fill: 'telea' (the reference's recipe, on the host; default) or 'pull_push' (device-side substitute of rounds 2-5)
         self.refiner_graphs = refiner_graphs      # None: the Tracker's default (no replay since round 6); True: refiner windows replayed as hipGraphs
         self.refiner_factory = None       # optional: callable(ft_channels) -> SegNetwork used instead of a default-initialised one
@@ -69,19 +71,22 @@ class Parameters:
             self.disc_params.update(fletcher_reeves=True, CG_forgetting_rate=None)
         self.refnet_params = AttrDict(layers=('layer5', 'layer4', 'layer3', 'layer2'), nchannels=64, use_batch_norm=True)
 
+    def make_refiner(self, chans):
+        """The refiner for backbone taps of `chans` channels (deep -> shallow), with the configured head."""
+        p = self.refnet_params
+        if self.refiner_factory is not None:                       # bench.py / tests: synthetic stand-in for a trained refiner
+            return self.refiner_factory(chans)
+        if self.weights is None:
+            torch.manual_seed(1)                                   # seeded default init (SURVEY.md 8d)
+        return SegNetwork(self.disc_params.out_channels, p.nchannels, chans, p.use_batch_norm, upsampler=self.upsampler)
+
     def get_model(self):
         augmenter = ImageAugmenter(self.aug_params, fill=self.aug_fill)
         extractor = ResnetFeatureExtractor(self.feature_extractor, weights=self.backbone_weights).to(self.device)
         self.disc_params.in_channels = extractor.get_out_channels()[self.disc_params.layer]
         p = self.refnet_params
         chans = {L: n for L, n in extractor.get_out_channels().items() if L in p.layers}
-        if self.refiner_factory is not None:                       # bench.py / tests: synthetic stand-in for a trained refiner
-            refiner = self.refiner_factory(chans)
-        elif self.weights is None:
-            torch.manual_seed(1)                                   # seeded default init
-            refiner = SegNetwork(self.disc_params.out_channels, p.nchannels, chans, p.use_batch_norm)
-        else:
-            refiner = SegNetwork(self.disc_params.out_channels, p.nchannels, chans, p.use_batch_norm)
+        refiner = self.make_refiner(chans)
         extra = {} if self.refiner_graphs is None else dict(refiner_graphs=bool(self.refiner_graphs))
         mdl = Tracker(augmenter, extractor, self.disc_params, refiner, self.device, feature_batch=self.feature_batch,
                       trunk_lanes=self.trunk_lanes, **extra)
@@ -91,18 +96,10 @@ class Parameters:
         return mdl
 
 
-def main(argv=None):
-    """``python -m frtm_vos_amd.evaluate --model rn101_all.pth --dset dv2017val --davis /data/DAVIS --output /tmp/out``
-    (reference evaluate.py:108-165).  One process per GPU: launched under torch.distributed.run, every rank takes
-    ``dataset[rank::world_size]`` (no collective on the data path) and rank 0 prints the aggregate frame rate."""
+def parse_args(argv=None):
+    """The command line of ``main`` (--ytvos-fork expanded into the options it stands for)."""
     import argparse
     import os
-    from pathlib import Path
-
-    from .lib.datasets import DAVISDataset, YouTubeVOSDataset
-    from .lib.evaluation import evaluate_dataset
-    from .shard import aggregate_throughput, shard_indices, write_rank_report
-
     ap = argparse.ArgumentParser(description='Evaluate FRTM on a validation dataset (MI355X-native hot path)')
     ap.add_argument('--model', required=True, help='FRTM checkpoint (.pth with the refiner weights)')
     ap.add_argument('--dset', required=True, choices=['dv2016val', 'dv2017val', 'yt2018val', 'yt2018jjval'])
@@ -115,6 +112,10 @@ def main(argv=None):
     ap.add_argument('--no-eval', action='store_true', help='skip the J / F evaluation after the run (reference evaluate.py:159-165 always evaluates)')
     ap.add_argument('--ytvos-merge', action='store_true', help="decode like the reference's YouTube-VOS fork (sequence-level merge, ground truth re-inserted)")
     ap.add_argument('--ytvos-solver', action='store_true', help="the fork's solver configuration: Fletcher-Reeves, CG state reset at every run (ytvos_validation/discriminator.py:256)")
+    ap.add_argument('--upsampler', choices=['compat', 'bicubic'], default='compat',
+                    help="refiner head: 'compat' (BackwardCompatibleUpsampler, the reference's default) or 'bicubic' (Upsampler, the fork's head)")
+    ap.add_argument('--ytvos-fork', action='store_true',
+                    help="a checkpoint of the reference's YouTube-VOS fork: shorthand for --ytvos-solver --ytvos-merge --upsampler bicubic")
     ap.add_argument('--dist-backend', default='nccl', help='nccl (= RCCL); gloo for tests')
     ap.add_argument('--share-gpu', action='store_true', help='tests only: every rank uses cuda:0')
     ap.add_argument('--prewarm', default=None, help='HxW: capture the graphs for this frame size (1-3 objects) before the first sequence')
@@ -123,6 +124,30 @@ def main(argv=None):
     ap.add_argument('--pull-push-fill', action='store_true', help="first-frame hole fill by the device-side pull-push pyramid (rounds 2-5) instead of Telea's fast-marching method on the host (the reference's cv2.inpaint recipe restated, the default)")
     ap.add_argument('--keep-gc', action='store_true', help="leave Python's cyclic collector alone (default: held off while a sequence is enqueued)")
     args = ap.parse_args(argv)
+    if args.ytvos_fork:
+        args.ytvos_solver, args.ytvos_merge, args.upsampler = True, True, 'bicubic'
+    return args
+
+
+def parameters_from_args(args, weights):
+    """Parameters of a parsed command line (main); the checkpoint `weights` as loaded from --model."""
+    return Parameters(weights, fast=args.fast, device=args.dev, ytvos_fork_solver=args.ytvos_solver,
+                      refiner_graphs=True if args.refiner_graphs else None, aug_fill='pull_push' if args.pull_push_fill else 'telea',
+                      upsampler=args.upsampler)
+
+
+def main(argv=None):
+    """``python -m frtm_vos_amd.evaluate --model rn101_all.pth --dset dv2017val --davis /data/DAVIS --output /tmp/out``
+    (reference evaluate.py:108-165).  One process per GPU: launched under torch.distributed.run, every rank takes
+    ``dataset[rank::world_size]`` (no collective on the data path) and rank 0 prints the aggregate frame rate."""
+    import os
+    from pathlib import Path
+
+    from .lib.datasets import DAVISDataset, YouTubeVOSDataset
+    from .lib.evaluation import evaluate_dataset
+    from .shard import aggregate_throughput, shard_indices, write_rank_report
+
+    args = parse_args(argv)
 
     rank, world = int(os.environ.get('RANK', 0)), int(os.environ.get('WORLD_SIZE', 1))
     coll, red_dev, dist_err = None, 'cpu', None
@@ -148,8 +173,7 @@ def main(argv=None):
     host_cpus = [] if (args.no_cpu_pin or args.share_gpu) else pin_host_threads_near_gpu(torch.device(args.dev).index or 0)
     if rank == 0:
         print('host threads: %s' % (('CPUs %d-%d (%d logical) near the GPU' % (min(host_cpus), max(host_cpus), len(host_cpus))) if host_cpus else 'not pinned'))
-    tracker = Parameters(weights, fast=args.fast, device=args.dev, ytvos_fork_solver=args.ytvos_solver,
-                         refiner_graphs=True if args.refiner_graphs else None, aug_fill='pull_push' if args.pull_push_fill else 'telea').get_model()
+    tracker = parameters_from_args(args, weights).get_model()
     if not args.keep_gc:
         # driver-level decisions (process-global, so not the library's): long-lived objects into the permanent generation once, and no
         # cyclic collection while a sequence's launches are being enqueued

@@ -13,6 +13,8 @@ Structural changes relative to the reference that leave the results unchanged:
  * ``TSE.reduce`` (two 1x1 convs on the backbone tap) does not depend on the object and is computed
    once per frame and tap (``precompute``), not once per object.
 Parameter names match the reference checkpoint ('refiner.TSE.layer4.reduce.0.weight', ...).
+Two heads (``project``) with the same checkpoint keys: ``BackwardCompatibleUpsampler`` (the reference's default) and ``Upsampler`` (its
+bicubic head, the only one of its YouTube-VOS fork; ``SegNetwork(..., upsampler='bicubic')``).  The HIP path dispatches on the head's type.
 """
 import torch
 from torch import nn
@@ -134,9 +136,33 @@ class BackwardCompatibleUpsampler(nn.Module):
         return self.conv2(x)
 
 
+class Upsampler(nn.Module):
+    """The reference's non-legacy head (model/seg_network.py:59-72; commented out at :174) and the only head of its YouTube-VOS fork
+    (ytvos_validation/seg_network.py:62-75,101): bicubic 2x, conv1, relu, bicubic to the image size, conv2.  Same state-dict keys as
+    BackwardCompatibleUpsampler (the resampling steps carry no parameters): a fork checkpoint loads into either head."""
+
+    def __init__(self, in_channels=64):
+        super().__init__()
+        self.conv1 = conv(in_channels, in_channels // 2, 3)
+        self.conv2 = conv(in_channels // 2, 1, 3)
+
+    def forward(self, x, image_size):
+        up = F.interpolate(x, (2 * x.shape[-2], 2 * x.shape[-1]), mode='bicubic', align_corners=False)
+        y = F.relu(self.conv1(up))
+        return self.conv2(F.interpolate(y, tuple(image_size[-2:]), mode='bicubic', align_corners=False))
+
+
+_HEADS = {'compat': BackwardCompatibleUpsampler, 'bicubic': Upsampler}
+
+
 class SegNetwork(nn.Module):
 
-    def __init__(self, in_channels=1, out_channels=32, ft_channels=None, use_bn=False):
+    def __init__(self, in_channels=1, out_channels=32, ft_channels=None, use_bn=False, upsampler='compat'):
+        """upsampler: 'compat' (BackwardCompatibleUpsampler, the reference's default) or 'bicubic' (Upsampler, the head of its
+        YouTube-VOS fork).  The HIP path dispatches on the type of ``self.project``, so assigning ``net.project = Upsampler(...)``
+        afterwards (the reference's commented-out line) works as well."""
+        if upsampler not in _HEADS:
+            raise ValueError('upsampler must be one of %s, not %r' % (sorted(_HEADS), upsampler))
         super().__init__()
         assert ft_channels is not None
         self.ft_channels = ft_channels
@@ -149,7 +175,7 @@ class SegNetwork(nn.Module):
             self.RRB1[L] = RRB(out_channels, use_bn=use_bn)
             self.CAB[L] = CAB(out_channels, L == 'layer5')
             self.RRB2[L] = RRB(out_channels, use_bn=use_bn)
-        self.project = BackwardCompatibleUpsampler(out_channels)
+        self.project = _HEADS[upsampler](out_channels)
         self.use_graphs = False       # set by the tracker when the backbone taps live at stable addresses
         self.parallel_eager = True    # without graphs: deep levels on the shared side stream (fork / join through events), else one stream
         self._graphs = {}
@@ -167,6 +193,11 @@ class SegNetwork(nn.Module):
         """Drop the packed HIP weights and captured graphs (call after editing parameters in place)."""
         self._pack_key = None
         self._graphs = {}
+
+    def __setattr__(self, name, value):
+        if isinstance(value, nn.Module) and '_pack_key' in self.__dict__:
+            self.invalidate()             # a swapped sub-module (e.g. the head): packed weights and captured graphs belong to the old one
+        super().__setattr__(name, value)
 
     def _apply(self, fn, *a, **k):
         self.invalidate()
@@ -315,7 +346,13 @@ class SegNetwork(nn.Module):
                         cab_w1=c[0].weight.data.flatten(1).t().contiguous(), cab_b1=c[0].bias.data.contiguous(), cab_w2=c[2].weight.data.flatten(1).t().contiguous(),
                         cab_b2=c[2].bias.data.contiguous())
         pj = self.project
-        P['project'] = dict(c1=cv(pj.conv1, relu_=True), w2=pj.conv2.weight.data.contiguous(), b2=pj.conv2.bias.data,
+        if isinstance(pj, Upsampler):                 # dispatch on the head's type: net.project may be swapped after construction
+            kind = 'bicubic'
+        elif isinstance(pj, BackwardCompatibleUpsampler):
+            kind = 'compat'
+        else:
+            raise TypeError('SegNetwork: no HIP path for the head %s' % type(pj).__name__)
+        P['project'] = dict(kind=kind, c1=cv(pj.conv1, relu_=True), w2=pj.conv2.weight.data.contiguous(), b2=pj.conv2.bias.data,
                             eye9=torch.eye(9, device=dev).contiguous())
         self._pack, self._pack_key = P, key
         return P
@@ -417,6 +454,8 @@ class SegNetwork(nn.Module):
             keep.append((x, gate, out, dp))
             x = self._rrb_hip(out, p['rrb2'])
         pj = P['project']
+        if pj['kind'] == 'bicubic':
+            return self._head_bicubic(x, pj, image_size)
         c, hh, ww = x.shape[1:]
         u1 = torch.empty(n, c, 2 * hh, 2 * ww, device=dev)
         H.call('frtm_pyrup2x', H.ptr(x), n * c, hh, ww, H.ptr(u1))
@@ -443,3 +482,36 @@ class SegNetwork(nn.Module):
             z = u2
         out = pj['b2'].view(1, 1, 1, 1).expand(n, 1, Ho, Wo).contiguous()
         return ops.filter_scores(z, pj['w2'], out=out, accumulate=True)
+
+    def _head_bicubic(self, x, pj, image_size):
+        """Upsampler.forward on the HIP kernels: 2x bicubic -> conv1 + relu -> bicubic resize to the image size -> conv2, the last two
+        fused (frtm_project_tail_bicubic) on conv2's nine tap maps (frtm_tap_mix) when the resize ratio fits the kernel's patch."""
+        n, c, hh, ww = x.shape
+        dev = x.device
+        # The 2x step is frtm_pyrup2x: at exactly 2x, bicubic F.interpolate samples at the offsets -0.25 / -0.75 of PyrUpBicubic2d and clamps its
+        # indices like its replicate padding, so the two are one operator (the GPU test holds pyrup2x to frtm_bicubic_resize at 2x within 1e-6
+        # relative); pyrup2x reads 10 inputs per 2x2 output quad where the general resize reads 16 per output.
+        u1 = torch.empty(n, c, 2 * hh, 2 * ww, device=dev)
+        H.call('frtm_pyrup2x', H.ptr(x), n * c, hh, ww, H.ptr(u1))
+        y = self._conv(u1, pj['c1'])
+        c2, h2, w2 = y.shape[1], 2 * hh, 2 * ww
+        Ho, Wo = int(image_size[-2]), int(image_size[-1])
+        if self.fuse_tail and bicubic_tail_fits(h2, w2, Ho, Wo):
+            out = torch.empty(n, 1, Ho, Wo, device=dev)
+            if self.mix_taps and c2 > 9:
+                ym = torch.empty(n, 9, h2, w2, device=dev)
+                H.call('frtm_tap_mix', H.ptr(y), n, c2, h2 * w2, H.ptr(pj['w2']), H.ptr(ym))
+                H.call('frtm_project_tail_bicubic', H.ptr(ym), n, 9, h2, w2, H.ptr(pj['eye9']), H.ptr(pj['b2']), Ho, Wo, H.ptr(out))
+            else:
+                H.call('frtm_project_tail_bicubic', H.ptr(y), n, c2, h2, w2, H.ptr(pj['w2']), H.ptr(pj['b2']), Ho, Wo, H.ptr(out))
+            return out
+        z = torch.empty(n, c2, Ho, Wo, device=dev)
+        H.call('frtm_bicubic_resize', H.ptr(y), n * c2, h2, w2, H.ptr(z), Ho, Wo)
+        out = pj['b2'].view(1, 1, 1, 1).expand(n, 1, Ho, Wo).contiguous()
+        return ops.filter_scores(z, pj['w2'], out=out, accumulate=True)
+
+
+def bicubic_tail_fits(h, w, Ho, Wo):
+    """Whether frtm_project_tail_bicubic takes a (h,w) -> (Ho,Wo) resize: the argument check of csrc/refiner_ops.hip (its 18 x 66 z patch
+    reads at most BT_YR = 16 source rows and BT_YC = 40 source columns), evaluated the same way."""
+    return int(17 * (h / Ho)) + 6 <= 16 and int(65 * (w / Wo)) + 6 <= 40

@@ -442,6 +442,16 @@ int frtm_project_tail(const float* y, int n, int C, int h, int w, const float* w
  * frtm_project_tail(out, n, 9, h, w, one-hot weights (9,3,3): eye(9), bias, ..) then equals frtm_project_tail(y, n, C, h, w, w3x3, bias, ..)
  * up to summation order, with 9 instead of C maps resampled (model/seg_network.py:117-119). */
 int frtm_tap_mix(const float* y, int n, int C, int hw, const float* w3x3, float* out, frtm_stream_t stream);
+/* F.interpolate(..., (H,W), 'bicubic', align_corners=False) of `planes` maps (model/seg_network.py: Upsampler), any ratio up or down:
+ * source coordinate (dst + 0.5) * in/out - 0.5 (no clamp at 0), taps floor - 1 .. floor + 2 clamped into the map, A = -0.75. */
+int frtm_bicubic_resize(const float* in, int planes, int h, int w, float* out, int H, int W, frtm_stream_t stream);
+/* Tail of Upsampler.forward (model/seg_network.py) in one kernel:
+ *   out[n,0] = conv2(interpolate(y[n], (Ho,Wo), bicubic, align_corners=False)) + bias
+ * y (n,C,h,w) is relu(conv1(2x bicubic(x))); conv2 = 3x3, C -> 1, zero padding.  w3x3 (1,C,3,3), bias (1) or NULL.  Takes the nine
+ * tap maps of frtm_tap_mix with one-hot weights like frtm_project_tail.  The upscale Ho/h, Wo/w must be at least ~1.6 x ~1.9 (the LDS
+ * patch of the fused kernel); otherwise the call fails with FRTM_ERR_ARG and the caller composes frtm_bicubic_resize + frtm_filter_scores. */
+int frtm_project_tail_bicubic(const float* y, int n, int C, int h, int w, const float* w3x3, const float* bias, int Ho, int Wo, float* out,
+                              frtm_stream_t stream);
 /* adaptive_avg_pool2d(x, 1): out[plane] = mean(in[plane]) */
 int frtm_plane_mean(const float* in, int planes, int HW, float* out, frtm_stream_t stream);
 
