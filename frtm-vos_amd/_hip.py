@@ -80,6 +80,7 @@ SIGNATURES = {
     'frtm_spin': (I, [I, P]),
     'frtm_clock_probe': (I, [I, P, P]),
     'frtm_conv_persistent_launches': (ctypes.c_long, []),
+    'frtm_conv_last_kernels': (ctypes.c_char_p, []),
     'frtm_telea_inpaint_u8': (I, [P, P, I, I, I, I, P]),
     'frtm_fastdiv_check': (ctypes.c_uint, [ctypes.c_uint, ctypes.c_uint]),
     'frtm_backbone_set_lanes': (I, [P, I]),

@@ -43,6 +43,12 @@ static inline void fill_divs(ConvParams& p, int bm) {
   p.dMt = fast_div((unsigned)((p.M + bm - 1) / bm));
 }
 
+// Which kernels the last frtm_conv2d / frtm_conv_pack_weights call of this thread launched (frtm_conv_last_kernels): the two entry points reset the
+// record, every launch in the conv translation units appends its kernel's name -- the demangled symbol without spaces and argument list, e.g.
+// "k_conv3x3_halo<64,2,2,16,2>" -- so that a test can assert which form a shape reached (tests/test_conv_forms_gpu.py).  Host only.
+void conv_trace_reset();
+void conv_trace(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
+
 constexpr int BK = 32;                 // K granularity of the packed weights / split-K bookkeeping
 constexpr unsigned OOB = 0x80000000u;   // byte offset beyond any buffer: raw buffer loads return 0 there
 

@@ -201,6 +201,7 @@ int launch_g32(const ConvParams& p, hipStream_t st) {
   }
   const int g = ceil_div(p.Ntot, T::BN) * ceil_div(p.M, T::BM);
   k_conv1x1_g32<FM, FN, WGM, WGN, ABL, ST><<<g, T::NT, lds, st>>>(p);
+  conv_trace("k_conv1x1_g32<%d,%d,%d,%d,%d,%d>", FM, FN, WGM, WGN, ABL, ST);
   return FRTM_OK;
 }
 

@@ -16,6 +16,8 @@
 //    tiles (32x64 / 64x64 / 128x64) plus split-K keep >= 256 workgroups in flight.
 #include <algorithm>
 #include <atomic>
+#include <cstdarg>
+#include <cstdio>
 #include <cstdlib>
 #include "frtm_common.h"
 #include "../../include/frtm_hip.h"
@@ -30,6 +32,19 @@ int frtm_wino4_pack(const float* w_oihw, int Cout, int Cin, float* U, int m, hip
 int frtm_wino4_launch(const ConvParams& p, float* ws, size_t ws_elems, int tile, int m, hipStream_t st);
 // conv_gemm32.hip
 int frtm_g32_launch(const ConvParams& p, int tile, hipStream_t st);
+
+static thread_local char t_conv_trace[256];        // space-separated kernel names (conv_common.h: conv_trace)
+static thread_local int t_conv_trace_len = 0;
+void conv_trace_reset() { t_conv_trace_len = 0; t_conv_trace[0] = 0; }
+void conv_trace(const char* fmt, ...) {
+  char name[96];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(name, sizeof(name), fmt, ap);
+  va_end(ap);
+  const int n = snprintf(t_conv_trace + t_conv_trace_len, sizeof(t_conv_trace) - t_conv_trace_len, t_conv_trace_len ? " %s" : "%s", name);
+  if (n > 0) t_conv_trace_len = std::min(t_conv_trace_len + n, (int)sizeof(t_conv_trace) - 1);
+}
 
 #ifdef FRTM_DEBUG_TRACE
 // tools/ktrace.py only (never in the shipped library): every workgroup of k_conv_igemm records where it ran and when its phases began --
@@ -575,6 +590,9 @@ __global__ __launch_bounds__(512) void k_conv_igemm_p(const ConvParams p) {
   using S0 = std::integral_constant<int, 0>;
   using S1 = std::integral_constant<int, 1>;
 
+  // A grid larger than the tile count (FRTM_PERSIST_MIN_ROUNDS_X2 below 2): the surplus workgroups have no tile.  tile_order is a bijection on
+  // [0, ntiles) only -- past it a workgroup would recompute (and store) another workgroup's tile.  Uniform, before the first barrier.
+  if ((int)blockIdx.x >= ntiles) return;
   int t = blockIdx.x;
   int m0 = setup_ab(t);
   e_off0 = e_next;
@@ -836,6 +854,7 @@ static void launch_tile_u(const ConvParams& p_, hipStream_t st) {
   fill_divs(p, BM);
   dim3 g(ceil_div(p.Ntot, BN) * ceil_div(p.M, BM), 1, p.splitk);
   k_conv_igemm<BM, BN, WGM, WGN, 2, 32><<<g, 64 * WGM * WGN, 0, st>>>(p);
+  conv_trace("k_conv_igemm<%d,%d,%d,%d,2,32>", BM, BN, WGM, WGN);
 }
 
 static std::atomic<long> g_persistent_launches{0};      // launches that took k_conv_igemm_p (frtm_conv_persistent_launches: tests assert that the form they mean to test ran)
@@ -871,12 +890,14 @@ static void launch_tile(const ConvParams& p_, bool vec1x1, hipStream_t st) {
         p.ntiles = (int)g.x;
         k_conv_igemm_p<<<G, 512, 0, st>>>(p);
         g_persistent_launches += 1;
+        conv_trace("k_conv_igemm_p");
         return;
       }
     }
   }
   if (vec1x1) k_conv_igemm<BM, BN, WGM, WGN, 1, BKT><<<g, 64 * WGM * WGN, 0, st>>>(p);
   else k_conv_igemm<BM, BN, WGM, WGN, 0, BKT><<<g, 64 * WGM * WGN, 0, st>>>(p);
+  conv_trace("k_conv_igemm<%d,%d,%d,%d,%d,%d>", BM, BN, WGM, WGN, vec1x1 ? 1 : 0, BKT);
 }
 
 // Chooses tile and split-K.  Measured on MI355X (tools/conv_bench.py --sweep, profiles/r01_conv_sweep.txt):
@@ -913,6 +934,7 @@ static void launch_halo(const ConvParams& p_, int tw, hipStream_t st) {
   p.dA = fast_div((unsigned)(ceil_div(p.Ho, th) * ceil_div(p.Wo, tw)));
   p.dB = fast_div((unsigned)ceil_div(p.Wo, tw));
   dim3 g(p.B * ceil_div(p.Ho, th) * ceil_div(p.Wo, tw) * ceil_div(p.M, BM), 1, p.splitk);
+  conv_trace("k_conv3x3_halo<%d,%d,%d,%d,%d>", BM, WGM, WGN, tw == 4 ? 4 : tw == 8 ? 8 : 16, p.stride == 2 ? 2 : 1);
   if (p.stride == 2) {
     if (tw == 4) k_conv3x3_halo<BM, WGM, WGN, 4, 2><<<g, 64 * WGM * WGN, 0, st>>>(p);
     else if (tw == 8) k_conv3x3_halo<BM, WGM, WGN, 8, 2><<<g, 64 * WGM * WGN, 0, st>>>(p);
@@ -968,6 +990,7 @@ extern "C" {
 
 int frtm_conv_pack_weights(const float* w_oihw, int Cout, int Cin, int ksize, int layout, float* wT, int* ktab,
                            frtm_stream_t stream) {
+  conv_trace_reset();
   FRTM_CHECK_ARG(w_oihw && wT && Cout > 0 && Cin > 0 && ksize > 0, "frtm_conv_pack_weights: bad argument");
   if (layout == FRTM_WLAYOUT_WINO3X3) {
     FRTM_CHECK_ARG(ksize == 3, "frtm_conv_pack_weights: the Winograd layout is for 3x3 kernels");
@@ -981,18 +1004,21 @@ int frtm_conv_pack_weights(const float* w_oihw, int Cout, int Cin, int ksize, in
     FRTM_CHECK_ARG(ksize == 3, "frtm_conv_pack_weights: the halo layout is for 3x3 kernels");
     const size_t total = (size_t)ceil_div(Cin, HCI) * HK * ((Cout + 31) / 32 * 32);
     k_pack_weights_halo<<<(int)min((total + 255) / 256, (size_t)2048), 256, 0, (hipStream_t)stream>>>(w_oihw, Cout, Cin, wT);
+    conv_trace("k_pack_weights_halo");
     FRTM_LAUNCH_CHECK();
     return FRTM_OK;
   }
   FRTM_CHECK_ARG(layout == FRTM_WLAYOUT_GEMM, "frtm_conv_pack_weights: unknown layout %d", layout);
   const size_t total = (size_t)((Cin * ksize * ksize + 31) / 32 * 32) * ((Cout + 31) / 32 * 32);
   k_pack_weights<<<(int)min((total + 255) / 256, (size_t)2048), 256, 0, (hipStream_t)stream>>>(w_oihw, Cout, Cin, ksize, wT, ktab);
+  conv_trace("k_pack_weights");
   FRTM_LAUNCH_CHECK();
   return FRTM_OK;
 }
 
 int frtm_conv2d(const frtm_conv_desc* d, const float* in, const float* wT, const int* ktab, const float* scale, const float* shift,
                 const float* residual, float* out, float* workspace, frtm_stream_t stream) {
+  conv_trace_reset();
   FRTM_CHECK_ARG(d && in && wT && out, "frtm_conv2d: null pointer");
   FRTM_CHECK_ARG(d->B > 0 && d->Cin > 0 && d->Cout > 0 && d->ksize > 0 && d->stride > 0 && d->pad >= 0, "frtm_conv2d: bad shape");
   FRTM_CHECK_ARG((scale == nullptr) == (shift == nullptr), "frtm_conv2d: scale and shift go together");
@@ -1110,6 +1136,7 @@ int frtm_conv2d(const frtm_conv_desc* d, const float* in, const float* wT, const
   if (p.splitk > 1) {
     const size_t total = (size_t)p.M * p.Ntot;
     k_splitk_epilogue<<<(int)min((total + 255) / 256, (size_t)1024), 256, 0, st>>>(p);
+    conv_trace("k_splitk_epilogue");
     FRTM_LAUNCH_CHECK();
   }
   return FRTM_OK;
@@ -1136,6 +1163,8 @@ extern "C" int frtm_debug_ktrace_counts(unsigned* counts) {
 #endif
 
 extern "C" long frtm_conv_persistent_launches(void) { return g_persistent_launches.load(); }
+
+extern "C" const char* frtm_conv_last_kernels(void) { return t_conv_trace; }
 
 // Host-side evaluation of FastDiv (conv_common.h) for tests/test_cpu_host.py: the same m, s and the same formula as fdiv() on the device.
 extern "C" unsigned frtm_fastdiv_check(unsigned n, unsigned d) {

@@ -428,6 +428,7 @@ __global__ __launch_bounds__(256) void k_pack_weights_wino(const float* __restri
 int frtm_wino_pack(const float* w_oihw, int Cout, int Cin, float* wT, hipStream_t st) {
   const size_t total = (size_t)ceil_div(Cin, WCI) * WCI * ceil_div(Cout, WBM) * WBM;
   k_pack_weights_wino<<<(int)std::min((total + 255) / 256, (size_t)2048), 256, 0, st>>>(w_oihw, Cout, Cin, wT);
+  conv_trace("k_pack_weights_wino");
   FRTM_LAUNCH_CHECK();
   return FRTM_OK;
 }
@@ -456,11 +457,14 @@ int frtm_wino_launch(ConvParams& p, int variant, hipStream_t st) {
     p.dA = fast_div((unsigned)(ceil_div(p.Ho, bh) * ceil_div(p.Wo, bw))); p.dB = fast_div((unsigned)ceil_div(p.Wo, bw)); }
   if (variant == 2) {
     k_conv3x3_wino<2, 0, 3><<<p.B * ceil_div(p.Ho, 8) * ceil_div(p.Wo, 16) * mt, 256, 0, st>>>(p);
+    conv_trace("k_conv3x3_wino<2,0,3>");
   } else if (variant == 3) {
     k_conv3x3_wino<2, 1, 3><<<p.B * ceil_div(p.Ho, 16) * ceil_div(p.Wo, 8) * mt, 256, 0, st>>>(p);
+    conv_trace("k_conv3x3_wino<2,1,3>");
   } else {
     // (96 registers, 18 KB of LDS: five workgroups per CU; measured 1-3 % ahead of four on the refiner's shapes, profiles/r05_wino_bench.txt)
     k_conv3x3_wino<1, 0, 5><<<p.B * ceil_div(p.Ho, 8) * ceil_div(p.Wo, 8) * mt, 256, 0, st>>>(p);
+    conv_trace("k_conv3x3_wino<1,0,5>");
   }
   FRTM_LAUNCH_CHECK();
   return FRTM_OK;

@@ -308,6 +308,7 @@ int frtm_wino4_pack(const float* w_oihw, int Cout, int Cin, float* U, int m, hip
   FRTM_HIP(hipMemsetAsync(U, 0, (size_t)NP * Kp * Mp * sizeof(float), st));
   if (m == 6) k_wino6_weights<<<ceil_div(Cout * Cin, 256), 256, 0, st>>>(w_oihw, Cout, Cin, Kp, Mp, U);
   else k_wino4_weights<<<ceil_div(Cout * Cin, 256), 256, 0, st>>>(w_oihw, Cout, Cin, Kp, Mp, U);
+  conv_trace(m == 6 ? "k_wino6_weights" : "k_wino4_weights");
   FRTM_LAUNCH_CHECK();
   return FRTM_OK;
 }
@@ -327,6 +328,7 @@ int frtm_wino4_launch(const ConvParams& p, float* ws, size_t ws_elems, int tile,
   dim3 g(ceil_div(Tp, 256), p.Cin);
   if (m == 6) k_wino6_input<<<g, 256, 0, st>>>(p.in, p.Cin, H, W, th, tw, T, Tp, V);
   else k_wino4_input<<<g, 256, 0, st>>>(p.in, p.Cin, H, W, th, tw, T, Tp, V);
+  conv_trace(m == 6 ? "k_wino6_input" : "k_wino4_input");
   FRTM_LAUNCH_CHECK();
   ConvParams q = {};
   q.in = V; q.wT = p.wT; q.out = Mb;
@@ -341,6 +343,7 @@ int frtm_wino4_launch(const ConvParams& p, float* ws, size_t ws_elems, int tile,
   dim3 go(ceil_div(T, 256), p.M);
   if (m == 6) k_wino6_output<<<go, 256, 0, st>>>(Mb, p.M, H, W, th, tw, T, Tp, p.scale, p.shift, p.residual, p.relu, p.out);
   else k_wino4_output<<<go, 256, 0, st>>>(Mb, p.M, H, W, th, tw, T, Tp, p.scale, p.shift, p.residual, p.relu, p.out);
+  conv_trace(m == 6 ? "k_wino6_output" : "k_wino4_output");
   FRTM_LAUNCH_CHECK();
   return FRTM_OK;
 }

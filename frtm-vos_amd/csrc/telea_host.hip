@@ -7,8 +7,8 @@
 // normalised by its own length -- with the SAME arithmetic (which operation is float, which double) so that the two agree bit for bit
 // (tests/test_cpu_host.py).  PARITY WITH OpenCV ITSELF IS UNPINNED, like the oracle's.
 //
-// It is an OPTION of the product (ImageAugmenter(fill='telea')): the default first-frame fill is the device-side pull-push pyramid
-// (csrc/image_ops.hip), whose effect on J&F against this fill is measured in profiles/r06_fill_evidence.txt.  Fast marching is sequential by
+// It is the product's default first-frame fill (ImageAugmenter(fill='telea')); the device-side pull-push pyramid (csrc/image_ops.hip, fill='pull_push')
+// is the alternative, and its effect on J&F against this fill is measured in profiles/r06_fill_evidence.txt.  Fast marching is sequential by
 // nature (a heap ordered by arrival time), which is why it runs on the host -- as it does in the reference.  No GPU involved: every pointer is host memory.
 #include <cmath>
 #include <cstdint>

@@ -355,12 +355,18 @@ int frtm_clock_probe(int microseconds, unsigned long long* out2, frtm_stream_t s
 /* HOST-side hole fill of the reference's first-frame augmentation: cv2.inpaint(image, hole, inpaintRadius = radius, cv2.INPAINT_TELEA)
  * (reference model/augmenter.py:317-324; the reference runs it on the CPU through OpenCV, once per object).  Restated from the published
  * fast-marching algorithm (csrc/telea_host.hip); every pointer is HOST memory, no GPU involved.  image / out: C planes of H x W uint8 (C <= 4),
- * hole: H x W, nonzero = pixel to fill.  An OPTION of the product (ImageAugmenter(fill='telea')); the default fill is frtm_pull_push_fill. */
+ * hole: H x W, nonzero = pixel to fill.  The product's default first-frame fill (ImageAugmenter(fill='telea')); frtm_pull_push_fill is the
+ * device-side alternative (fill='pull_push'). */
 int frtm_telea_inpaint_u8(const unsigned char* image_chw, const unsigned char* hole_hw, int C, int H, int W, int radius, unsigned char* out_chw);
 /* Launches of frtm_conv2d (this process) that took the PERSISTENT form of the 64x64 / 8-wave GEMM kernel (csrc/conv_igemm.hip: k_conv_igemm_p, round 6):
  * stride-1 1x1 convs with Cout % 64 == 0, Cin % 64 == 0, H*W % 4 == 0 and at least 1.5 tiles per resident workgroup.  FRTM_NO_PERSIST_GEMM=1 switches
  * the form off (A/B; results are bit-identical either way). */
 long frtm_conv_persistent_launches(void);
+/* The kernels that the last frtm_conv2d or frtm_conv_pack_weights call OF THE CALLING THREAD launched, space-separated in launch order, each named as its
+ * demangled symbol without spaces and argument list: "k_conv3x3_halo<64,2,2,16,2> k_splitk_epilogue", "k_conv_igemm_p", "k_wino4_input
+ * k_conv_igemm<64,64,2,4,1,32> k_wino4_output", ...  Empty after a call that failed before launching.  Host-side bookkeeping for the tests that
+ * must know which kernel form a shape reached (tests/test_conv_forms_gpu.py); the pointer stays valid until the thread's next such call. */
+const char* frtm_conv_last_kernels(void);
 /* Host-side check of the multiplication the conv kernels use instead of integer divisions in their index arithmetic (csrc/conv_common.h: FastDiv,
  * q = (mulhi(n, m) + n) >> s with m, s prepared per divisor): returns n / d as that formula computes it, for 0 <= n < 2^31, d >= 1.
  * No GPU involved; tests/test_cpu_host.py sweeps it against Python's integer division. */
