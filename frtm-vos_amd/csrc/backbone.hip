@@ -18,6 +18,7 @@ struct ConvL {
   float* wW = nullptr;          // 3x3 stride-1 convs: second image of the weights, Winograd F(2x2,3x3) (FRTM_WLAYOUT_WINO3X3)
   float* wW4 = nullptr;         // ... with >= 128 channels: third image, the 36 matrices of Winograd F(4x4,3x3) (FRTM_WLAYOUT_WINO4)
   float* wW6 = nullptr;         // ... and the 64 matrices of F(6x6,3x3) (FRTM_WLAYOUT_WINO6)
+  float* wB = nullptr;          // convs a bf16x3 trunk routes (bf16x3_packs), bf16x3 trunks only: the three bf16 pieces (FRTM_WLAYOUT_BF16X3), packed lazily
   bool loaded = false;
   int layout = 0;
   // per-conv launch plan (frtm_backbone_set_conv_plan; 0 = the planner's choice): the GEMM tile of the path the conv takes (direct 1x1 /
@@ -55,6 +56,7 @@ struct frtm_backbone {
   int use_winograd4 = getenv("FRTM_NO_WINO4") ? 0 : getenv("FRTM_NO_WINO6") ? 1 : 2;
   // fewest 64x64 product tiles for which the three-launch forms are taken (256 = one per CU: measured at batch 1 -- the streaming path -- 2.49 -> 2.23 ms per trunk pass; FRTM_WINO4_MIN_TILES)
   int wino4_min_tiles = getenv("FRTM_WINO4_MIN_TILES") ? atoi(getenv("FRTM_WINO4_MIN_TILES")) : 256;
+  int precision = 0;           // frtm_backbone_set_precision: 0 = fp32, 1 = bf16x3 for the routed stride-1 1x1 convs (bf16x3_route)
   int generation = 0;          // bumped whenever an arena / workspace is (re)allocated: captured graphs of older generations are stale
 };
 
@@ -176,6 +178,22 @@ static int scanned_tile(const ConvL& c, int B, int Ho, int Wo, bool products) {
   return 0;
 }
 
+int frtm_bf16x3_pack(const float* src, int Cout, int Cin, int sm, int sk, float* out, hipStream_t st);
+
+static bool bf16x3_eligible(const ConvL& c) { return c.ks == 1 && c.stride == 1 && c.pad == 0 && c.Cin % 16 == 0; }
+
+// The convs a bf16x3 trunk sends to the bf16x3 kernel: only where it measured faster than the fp32 form (DESIGN.md section 4,
+// profiles/bf16x3_trunk_time.txt): layer4's conv3 (512 -> 2048) with at least 3240 columns in the launch (8 frames of 480x854: 61 against 69 us).
+// Every other trunk 1x1 shape, and this one at 1 frame, measured slower (0.27-0.98x), so they stay fp32.
+static bool bf16x3_packs(const ConvL& c) { return bf16x3_eligible(c) && c.Cin == 512 && c.Cout == 2048; }
+static bool bf16x3_route(const ConvL& c, int B, int Ho, int Wo) { return bf16x3_packs(c) && (long)B * Ho * Wo >= 3240; }
+
+// the split image of an eligible conv from its packed GEMM image wT[Kp][Mp32] (w(m, k) = wT[k * Mp32 + m])
+static int pack_bf16x3(ConvL& c, hipStream_t st) {
+  if (!c.wB) FRTM_HIP(hipMalloc((void**)&c.wB, FRTM_CONV_BF16X3_ELEMS(c.Cout, c.Cin) * sizeof(float)));
+  return frtm_bf16x3_pack(c.wT, c.Cout, c.Cin, 1, (c.Cout + 31) / 32 * 32, c.wB, st);
+}
+
 static int run_conv(frtm_backbone* bb, Lane& ln, int idx, int B, int Hin, int Win, const float* in, const float* residual, int relu,
                     float* out, int* Ho, int* Wo, hipStream_t st, int pad_override = -1) {
   ConvL& c = bb->convs[idx];
@@ -239,6 +257,11 @@ static int run_conv(frtm_backbone* bb, Lane& ln, int idx, int B, int Hin, int Wi
   }
   bb->last_flops_exec += 2.0 * c.Cout * (double)B * (*Ho) * (*Wo) * c.Cin * c.ks * c.ks;
   bb->last_flops_form[0] += 2.0 * c.Cout * (double)B * (*Ho) * (*Wo) * c.Cin * c.ks * c.ks;
+  if (bb->precision == 1 && c.wB && !c.plan_tile && !c.plan_splitk && bf16x3_route(c, B, *Ho, *Wo)) {
+    d.w_layout = FRTM_WLAYOUT_BF16X3;
+    d.splitk = 1;
+    return frtm_conv2d(&d, in, c.wB, nullptr, c.scale, c.shift, residual, out, nullptr, st);
+  }
   d.tile = c.plan_tile ? c.plan_tile : scanned_tile(c, B, *Ho, *Wo, false);
   d.splitk = c.plan_splitk;
   return frtm_conv2d(&d, in, c.wT, c.ktab, c.scale, c.shift, residual, out, ln.ws, st);
@@ -400,6 +423,7 @@ int frtm_backbone_destroy(frtm_backbone_t* bb) {
     if (c.wW) (void)hipFree(c.wW);
     if (c.wW4) (void)hipFree(c.wW4);
     if (c.wW6) (void)hipFree(c.wW6);
+    if (c.wB) (void)hipFree(c.wB);
     if (c.scale) (void)hipFree(c.scale);
     if (c.shift) (void)hipFree(c.shift);
     if (c.ktab) (void)hipFree(c.ktab);
@@ -449,6 +473,10 @@ int frtm_backbone_set_conv(frtm_backbone_t* bb, int idx, const float* w_oihw, co
   c.layout = (c.ks == 3 && c.stride <= 2 && c.pad == 1) ? FRTM_WLAYOUT_HALO3X3 : FRTM_WLAYOUT_GEMM;
   int rc = frtm_conv_pack_weights(w_oihw, c.Cout, c.Cin, c.ks, c.layout, c.wT, c.ktab, stream);
   if (rc) return rc;
+  if (bf16x3_packs(c) && (c.wB || bb->precision == 1)) {
+    rc = pack_bf16x3(c, st);
+    if (rc) return rc;
+  }
   if (c.ks == 3 && c.stride == 1 && c.pad == 1) {
     if (!c.wW) FRTM_HIP(hipMalloc((void**)&c.wW, (size_t)FRTM_CONV_WINO_ELEMS(c.Cout, c.Cin) * sizeof(float)));
     rc = frtm_conv_pack_weights(w_oihw, c.Cout, c.Cin, 3, FRTM_WLAYOUT_WINO3X3, c.wW, nullptr, stream);
@@ -476,6 +504,25 @@ int frtm_backbone_generation(const frtm_backbone_t* bb) { return bb ? bb->genera
 int frtm_backbone_set_winograd(frtm_backbone_t* bb, int enable) {
   FRTM_CHECK_ARG(bb, "frtm_backbone_set_winograd: null handle");
   bb->use_winograd = enable != 0;
+  return FRTM_OK;
+}
+
+int frtm_backbone_set_precision(frtm_backbone_t* bb, int mode) {
+  FRTM_CHECK_ARG(bb, "frtm_backbone_set_precision: null handle");
+  FRTM_CHECK_ARG(mode == 0 || mode == 1, "frtm_backbone_set_precision: mode must be 0 (fp32) or 1 (bf16x3), got %d", mode);
+  bool pack = false;
+  for (auto& c : bb->convs) pack |= mode == 1 && c.loaded && bf16x3_packs(c) && !c.wB;
+  if (pack) {            // a configuration call, not a stream operation: the GEMM images may come from any stream, and the split ones are ready on return
+    FRTM_HIP(hipDeviceSynchronize());
+    for (auto& c : bb->convs)
+      if (c.loaded && bf16x3_packs(c) && !c.wB) {
+        int rc = pack_bf16x3(c, nullptr);
+        if (rc) return rc;
+      }
+    FRTM_HIP(hipDeviceSynchronize());
+  }
+  if (mode != bb->precision) bb->generation += 1;       // captured graphs hold the other kernels
+  bb->precision = mode;
   return FRTM_OK;
 }
 

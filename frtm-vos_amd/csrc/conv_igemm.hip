@@ -32,6 +32,9 @@ int frtm_wino4_pack(const float* w_oihw, int Cout, int Cin, float* U, int m, hip
 int frtm_wino4_launch(const ConvParams& p, float* ws, size_t ws_elems, int tile, int m, hipStream_t st);
 // conv_gemm32.hip
 int frtm_g32_launch(const ConvParams& p, int tile, hipStream_t st);
+// conv_bf16x3.hip
+int frtm_bf16x3_pack(const float* src, int Cout, int Cin, int sm, int sk, float* out, hipStream_t st);
+int frtm_bf16x3_launch(ConvParams p, hipStream_t st);
 
 static thread_local char t_conv_trace[256];        // space-separated kernel names (conv_common.h: conv_trace)
 static thread_local int t_conv_trace_len = 0;
@@ -1000,6 +1003,10 @@ int frtm_conv_pack_weights(const float* w_oihw, int Cout, int Cin, int ksize, in
     FRTM_CHECK_ARG(ksize == 3, "frtm_conv_pack_weights: the Winograd F(4x4,3x3) / F(6x6,3x3) layouts are for 3x3 kernels");
     return frtm_wino4_pack(w_oihw, Cout, Cin, wT, layout == FRTM_WLAYOUT_WINO6 ? 6 : 4, (hipStream_t)stream);
   }
+  if (layout == FRTM_WLAYOUT_BF16X3) {
+    FRTM_CHECK_ARG(ksize == 1, "frtm_conv_pack_weights: the bf16x3 layout is for 1x1 kernels");
+    return frtm_bf16x3_pack(w_oihw, Cout, Cin, Cin, 1, wT, (hipStream_t)stream);
+  }
   if (layout == FRTM_WLAYOUT_HALO3X3) {
     FRTM_CHECK_ARG(ksize == 3, "frtm_conv_pack_weights: the halo layout is for 3x3 kernels");
     const size_t total = (size_t)ceil_div(Cin, HCI) * HK * ((Cout + 31) / 32 * 32);
@@ -1056,6 +1063,11 @@ int frtm_conv2d(const frtm_conv_desc* d, const float* in, const float* wT, const
     FRTM_CHECK_ARG(d->ksize == 3 && d->stride == 1 && d->pad == 1 && d->w_pitch == 0 && !d->out_transposed,
                    "frtm_conv2d: the Winograd F(4x4,3x3) / F(6x6,3x3) layouts need 3x3, stride 1, pad 1, NCHW output");
     return frtm_wino4_launch(p, workspace, (size_t)d->ws_elems, d->tile, d->w_layout == FRTM_WLAYOUT_WINO6 ? 6 : 4, (hipStream_t)stream);
+  }
+  if (d->w_layout == FRTM_WLAYOUT_BF16X3) {
+    FRTM_CHECK_ARG(d->ksize == 1 && d->stride == 1 && d->pad == 0 && d->w_pitch == 0 && !d->out_transposed && d->tile == 0 && d->splitk >= 0 && d->splitk <= 1,
+                   "frtm_conv2d: the bf16x3 layout needs a 1x1 conv, stride 1, pad 0, NCHW output, w_pitch 0, tile 0 and no split-K");
+    return frtm_bf16x3_launch(p, (hipStream_t)stream);
   }
   const bool is1x1 = (d->ksize == 1 && d->pad == 0);
   FRTM_CHECK_ARG(is1x1 || ktab || d->w_layout == FRTM_WLAYOUT_HALO3X3, "frtm_conv2d: ktab required for ksize > 1");

@@ -21,8 +21,11 @@ class AttrDict(dict):
 class Parameters:
 
     def __init__(self, weights=None, fast=False, device='cuda:0', feature_extractor=None, backbone_weights=None, feature_batch=16, trunk_lanes=2,
-                 ytvos_fork_solver=False, refiner_graphs=None, aug_fill='telea', upsampler='compat'):
+                 ytvos_fork_solver=False, refiner_graphs=None, aug_fill='telea', upsampler='compat', trunk_precision='fp32'):
         self.device = device
+        if trunk_precision not in ('fp32', 'bf16x3'):
+            raise ValueError("trunk_precision must be 'fp32' or 'bf16x3', got %r" % (trunk_precision,))
+        self.trunk_precision = trunk_precision    # 'fp32' or 'bf16x3': the trunk's stride-1 1x1 convs on bf16 pieces (ResnetFeatureExtractor.precision)
         self.upsampler = upsampler                # refiner head: 'compat' (BackwardCompatibleUpsampler, the reference's default) or 'bicubic'
         #                                           (Upsampler, the head of the YouTube-VOS fork); both load the same checkpoint keys
         self.aug_fill = aug_fill                  # first-frame hole fill: 'telea' (the reference's recipe, on the host; default) or 'pull_push' (device-side substitute of rounds 2-5)
@@ -82,7 +85,7 @@ class Parameters:
 
     def get_model(self):
         augmenter = ImageAugmenter(self.aug_params, fill=self.aug_fill)
-        extractor = ResnetFeatureExtractor(self.feature_extractor, weights=self.backbone_weights).to(self.device)
+        extractor = ResnetFeatureExtractor(self.feature_extractor, weights=self.backbone_weights, precision=self.trunk_precision).to(self.device)
         self.disc_params.in_channels = extractor.get_out_channels()[self.disc_params.layer]
         p = self.refnet_params
         chans = {L: n for L, n in extractor.get_out_channels().items() if L in p.layers}
@@ -116,6 +119,9 @@ def parse_args(argv=None):
                     help="refiner head: 'compat' (BackwardCompatibleUpsampler, the reference's default) or 'bicubic' (Upsampler, the fork's head)")
     ap.add_argument('--ytvos-fork', action='store_true',
                     help="a checkpoint of the reference's YouTube-VOS fork: shorthand for --ytvos-solver --ytvos-merge --upsampler bicubic")
+    ap.add_argument('--trunk-precision', choices=['fp32', 'bf16x3'], default='fp32',
+                    help="'bf16x3': the routed stride-1 1x1 trunk convs on three bf16 pieces per operand (not bitwise fp32: 0.78-1.40x the fp32 kernels' max error against fp64; "
+                         "no measurable speed-up of the trunk or the tracker; README, DESIGN.md section 4)")
     ap.add_argument('--dist-backend', default='nccl', help='nccl (= RCCL); gloo for tests')
     ap.add_argument('--share-gpu', action='store_true', help='tests only: every rank uses cuda:0')
     ap.add_argument('--prewarm', default=None, help='HxW: capture the graphs for this frame size (1-3 objects) before the first sequence')
@@ -133,7 +139,7 @@ def parameters_from_args(args, weights):
     """Parameters of a parsed command line (main); the checkpoint `weights` as loaded from --model."""
     return Parameters(weights, fast=args.fast, device=args.dev, ytvos_fork_solver=args.ytvos_solver,
                       refiner_graphs=True if args.refiner_graphs else None, aug_fill='pull_push' if args.pull_push_fill else 'telea',
-                      upsampler=args.upsampler)
+                      upsampler=args.upsampler, trunk_precision=args.trunk_precision)
 
 
 def main(argv=None):

@@ -115,12 +115,17 @@ class ResNetParams(nn.Module):
         return self
 
 
+_PRECISIONS = {'fp32': 0, 'bf16x3': 1}     # frtm_backbone_set_precision modes
+
+
 class ResnetFeatureExtractor:
 
-    def __init__(self, name='resnet101', weights=None, seed=0):
-        """weights: None (env FRTM_RESNET_WEIGHTS or seeded synthetic), a state dict, or a path to one."""
+    def __init__(self, name='resnet101', weights=None, seed=0, precision='fp32'):
+        """weights: None (env FRTM_RESNET_WEIGHTS or seeded synthetic), a state dict, or a path to one.  precision: see the property."""
         if name not in _SPECS:
             raise ValueError('unknown backbone %r' % (name,))
+        if precision not in _PRECISIONS:
+            raise ValueError('precision must be one of %s, got %r' % (sorted(_PRECISIONS), precision))
         self.name = name
         self.arch = _SPECS[name][0]
         self.resnet = ResNetParams(name)
@@ -158,6 +163,7 @@ class ResnetFeatureExtractor:
         self._winograd = True
         self._winograd4 = not os.environ.get('FRTM_NO_WINO4')
         self._winograd6 = not os.environ.get('FRTM_NO_WINO6')
+        self._precision = precision
         self.use_graph = False         # with reuse_outputs: replay a captured hipGraph per (batch, size) instead of enqueuing the launches
         self.capture_after = 1         # trunk shapes are replayed as hipGraphs from their (capture_after + 1)-th use on
         self._pass_done = {}           # lane set -> event behind its last pass: a lane set (arenas, scratch) runs one pass at a time
@@ -188,6 +194,22 @@ class ResnetFeatureExtractor:
 
     def _wino_mode(self):
         return 0 if not self._winograd4 else 2 if self._winograd6 else 1
+
+    @property
+    def precision(self):
+        """'fp32' (default) or 'bf16x3': the trunk's stride-1 1x1 convs on three bf16 pieces per operand (frtm_backbone_set_precision; the
+        error bound and the routed shapes: DESIGN.md sections 4 and 9).  Every other conv stays fp32."""
+        return self._precision
+
+    @precision.setter
+    def precision(self, mode):
+        if mode not in _PRECISIONS:
+            raise ValueError('precision must be one of %s, got %r' % (sorted(_PRECISIONS), mode))
+        if self._handle is not None:
+            with torch.cuda.device(self.device):
+                H.call_nostream('frtm_backbone_set_precision', self._handle, _PRECISIONS[mode])      # raises: the mode stays as it was
+            self._out_cache.clear()           # captured graphs hold the other kernels
+        self._precision = mode
 
     @winograd4.setter
     def winograd4(self, on):
@@ -258,6 +280,7 @@ class ResnetFeatureExtractor:
                 H.call('frtm_backbone_set_conv', self._handle, i, H.ptr(cv.weight.data.float().contiguous()),
                        H.ptr(scale), H.ptr(shift))
             torch.cuda.current_stream().synchronize()      # the temporaries above die with this scope
+            H.call_nostream('frtm_backbone_set_precision', self._handle, _PRECISIONS[self._precision])
 
     def lane_streams(self):
         """The native trunk's internal streams (lanes 1.. of set 0) as torch streams: a caller that runs other work NEXT TO a pass places

@@ -36,14 +36,24 @@ def padded_cols(M):
     return (M + 31) // 32 * 32
 
 
-def pack_weights(w_oihw, halo=None, wino=False, wino4=False, wino6=False):
+def bf16x3_elems(Cout, Cin):
+    """Floats of a FRTM_WLAYOUT_BF16X3 image (FRTM_CONV_BF16X3_ELEMS): three bf16 planes [Cin/8][Mp][8], Mp = Cout rounded up to 128."""
+    return 3 * ((Cin + 15) // 16 * 16) * ((Cout + 127) // 128 * 128) // 2
+
+
+def pack_weights(w_oihw, halo=None, wino=False, wino4=False, wino6=False, bf16x3=False):
     """(Cout,Cin,k,k) -> packed GEMM weights (+ ktab for k > 1).  3x3 kernels default to the halo layout
     (valid for pad-1 convs of stride 1 or 2); wino=True: Winograd F(2x2,3x3) image (stride 1, pad 1); wino4=True: the 36 transformed
     weight matrices of Winograd F(4x4,3x3) (FRTM_WLAYOUT_WINO4; conv2d then needs ``ws`` = wino4_workspace(...)); wino6=True: the 64 of
-    F(6x6,3x3) (FRTM_WLAYOUT_WINO6, ``ws`` = wino4_workspace(..., m=6)).
+    F(6x6,3x3) (FRTM_WLAYOUT_WINO6, ``ws`` = wino4_workspace(..., m=6)); bf16x3=True: the three bf16 pieces of a 1x1 kernel (FRTM_WLAYOUT_BF16X3,
+    Cin % 16 == 0; conv2d with ``w_layout=5``).
     Returns (wT, ktab, layout)."""
     w = w_oihw.detach().float().contiguous()
     Cout, Cin, k, _ = w.shape
+    if bf16x3:
+        wT = torch.zeros(bf16x3_elems(Cout, Cin), device=w.device)
+        H.call('frtm_conv_pack_weights', H.ptr(w), Cout, Cin, k, 5, H.ptr(wT), None)
+        return wT, None, 5
     layout = 4 if wino6 else 3 if wino4 else 2 if wino else (1 if (halo if halo is not None else k == 3) else 0)
     rows = 64 * padded_rows(Cin) if layout == 4 else 36 * padded_rows(Cin) if layout == 3 else max(padded_rows(Cin * k * k), (Cin + 7) // 8 * 72) if layout != 2 else (Cin + 7) // 8 * 128
     wT = torch.zeros(rows, padded_cols(Cout), device=w.device)

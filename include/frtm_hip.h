@@ -263,7 +263,7 @@ typedef struct {
   int relu, out_transposed;
   int splitk;              /* 0 = auto */
   int tile;                /* 0 = auto, else FRTM_TILE_* */
-  int w_layout;            /* FRTM_WLAYOUT_GEMM (0) or FRTM_WLAYOUT_HALO3X3 (3x3, stride 1 or 2, pad 1 only) */
+  int w_layout;            /* FRTM_WLAYOUT_GEMM (0) or FRTM_WLAYOUT_HALO3X3 (3x3, stride 1 or 2, pad 1 only), ... FRTM_WLAYOUT_BF16X3 (below) */
   int ws_elems;            /* capacity of `workspace` in floats (0 = no workspace: split-K is disabled); split-K is clamped to it.
                               One workspace must not be used by convolutions that may run concurrently (one per stream). */
   int w_pitch;             /* 0: wT is the padded [Kp][Mp] image of frtm_conv_pack_weights;
@@ -293,6 +293,15 @@ typedef struct {
 #define FRTM_CONV_WINO6_ELEMS(Cout, Cin) (64 * (((Cin) + 31) / 32 * 32) * (((Cout) + 31) / 32 * 32))
 #define FRTM_CONV_WINO6_TILES(B, H, W) ((((B) * (((H) + 5) / 6) * (((W) + 5) / 6)) + 63) / 64 * 64)
 #define FRTM_CONV_WINO6_WS_ELEMS(B, Cin, Cout, H, W) ((size_t)64 * ((Cin) + (Cout)) * FRTM_CONV_WINO6_TILES(B, H, W))
+/* bf16x3 (opt-in precision mode, csrc/conv_bf16x3.hip): 1x1, stride 1, pad 0, NCHW output, w_pitch 0, Cin % 16 == 0, tile 0, splitk 0 or 1;
+   any Cout and H*W.  Weights and activations are split into three bf16 pieces (v = hi + mid + lo) and each product is formed from six piece
+   products (hi.hi, hi.mid, mid.hi, hi.lo, mid.mid, lo.hi) on bf16 MFMAs with fp32 accumulation.  NOT bitwise an fmaf chain: against an fp64 product,
+   on the trunk's 1x1 shapes at 1 and 8 frames, its max error is 0.78-1.40x and its rms error 0.93-1.28x those of the fp32 kernels
+   (profiles/bf16x3_trunk_time.txt).  A NaN input stays a NaN; an Inf input gives NaN.
+   Deterministic: bit-identical from launch to launch and for any grid.  The image is three bf16 planes [3][Cin/8][Mp][8], Mp = Cout rounded up
+   to 128, stored in a float buffer of FRTM_CONV_BF16X3_ELEMS floats (16-byte aligned).  Other descriptors return FRTM_ERR_ARG. */
+#define FRTM_WLAYOUT_BF16X3 5
+#define FRTM_CONV_BF16X3_ELEMS(Cout, Cin) ((size_t)3 * (((Cin) + 15) / 16 * 16) * (((Cout) + 127) / 128 * 128) / 2)
 #define FRTM_WINO_MIN_BLOCKS 512   /* 8x8 output blocks x 32-channel tiles below which callers prefer HALO3X3 + split-K */
 #define FRTM_CONV_PACKED_ELEMS(Cout, Cin, k) \
   (((((Cin) * (k) * (k) + 31) / 32 * 32) > (((Cin) + 7) / 8 * 72) ? (((Cin) * (k) * (k) + 31) / 32 * 32) : (((Cin) + 7) / 8 * 72)) * (((Cout) + 31) / 32 * 32))
@@ -367,6 +376,8 @@ long frtm_conv_persistent_launches(void);
  * k_conv_igemm<64,64,2,4,1,32> k_wino4_output", ...  Empty after a call that failed before launching.  Host-side bookkeeping for the tests that
  * must know which kernel form a shape reached (tests/test_conv_forms_gpu.py); the pointer stays valid until the thread's next such call. */
 const char* frtm_conv_last_kernels(void);
+/* Launches of frtm_conv2d (this process) that took the bf16x3 form (FRTM_WLAYOUT_BF16X3, csrc/conv_bf16x3.hip). */
+long frtm_conv_bf16x3_launches(void);
 /* Host-side check of the multiplication the conv kernels use instead of integer divisions in their index arithmetic (csrc/conv_common.h: FastDiv,
  * q = (mulhi(n, m) + n) >> s with m, s prepared per divisor): returns n / d as that formula computes it, for 0 <= n < 2^31, d >= 1.
  * No GPU involved; tests/test_cpu_host.py sweeps it against Python's integer division. */
@@ -395,6 +406,10 @@ int frtm_backbone_set_winograd(frtm_backbone_t* bb, int enable);
 /* Three-launch Winograd (FRTM_WLAYOUT_WINO4 / WINO6) for the eligible 3x3 convs of a Winograd-enabled trunk: 0 = off, 1 = F(4x4,3x3)
    only, 2 (default) = F(4x4,3x3) or F(6x6,3x3), whichever needs fewer products for the map at hand. */
 int frtm_backbone_set_winograd4(frtm_backbone_t* bb, int enable);
+/* Trunk precision: 0 = fp32 (default), 1 = bf16x3 -- the stride-1 1x1 convs that the router picks run as FRTM_WLAYOUT_BF16X3,
+ * in both lane sets and every lane; a per-conv plan (frtm_backbone_set_conv_plan) keeps its conv on the fp32 path.  The split weight images are
+ * packed when mode 1 is first set (and again by a later frtm_backbone_set_conv); mode 0 allocates nothing.  Bumps the generation. */
+int frtm_backbone_set_precision(frtm_backbone_t* bb, int mode);
 
 /* ------------------------------------------------------------------------------------------
  * Tracker.track mask merge (model/tracker.py:214-221), in place on masks (n_obj+1, H*W).
