@@ -99,6 +99,19 @@ SIGNATURES = {
     'frtm_cab_combine': (I, [P, P, P, I, I, I, I, I, I, I, P, P]),
     'frtm_pyrup2x': (I, [P, I, I, I, P, P]),
     'frtm_plane_mean': (I, [P, I, I, P, P]),
+    'frtm_conv_wgrad_ws_elems': (ctypes.c_size_t, [I, I, I, I, I, I]),
+    'frtm_conv_wgrad': (I, [P, P, I, I, I, I, I, I, P, P, P, ctypes.c_size_t, P]),
+    'frtm_bn_stats': (I, [P, I, I, I, F, F, I, P, P, P, P, P, P]),
+    'frtm_bn_apply_relu': (I, [P, P, P, P, P, I, I, I, P, P]),
+    'frtm_bn_relu_backward': (I, [P, P, P, P, P, P, I, I, I, I, P, P, P, P, P]),
+    'frtm_relu_backward': (I, [P, P, ctypes.c_size_t, P, P]),
+    'frtm_pyrup2x_backward': (I, [P, I, I, I, P, P, P]),
+    'frtm_bilinear_backward': (I, [P, I, I, I, I, I, P, P, P]),
+    'frtm_cab_backward_reduce': (I, [P, P, I, I, P, P, P]),
+    'frtm_cab_gate_backward': (I, [P, P, P, P, P, P, P, P, I, I, P, P, P, P, P, P, P]),
+    'frtm_cab_backward_shallow': (I, [P, P, P, I, I, P, P]),
+    'frtm_add_plane': (I, [P, P, F, I, I, P]),
+    'frtm_shift9': (I, [P, I, I, I, P, P]),
     'frtm_cab_gate': (I, [P, P, I, P, P, P, P, I, I, P, P]),
     'frtm_project_tail': (I, [P, I, I, I, I, P, P, I, I, P, P]),
     'frtm_tap_mix': (I, [P, I, I, I, P, P, P]),

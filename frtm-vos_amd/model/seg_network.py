@@ -7,6 +7,7 @@ SURVEY.md 8f row "next-1".  Two execution paths with identical results:
    HIP kernel each (csrc/refiner_ops.hip).  ~80 launches per frame instead of ~370 framework launches.
  * ``forward_torch``: plain PyTorch ops (the definition of the network; taken for CPU tensors, and called explicitly for training
    and as the definition the HIP path is tested against -- ``forward`` never falls back to it silently on the GPU: it raises).
+ * ``forward_train``: the training pass with autograd on HIP kernels (model/refiner_train.py, csrc/refiner_train.hip).
 Structural changes relative to the reference that leave the results unchanged:
  * all objects of a frame go through ONE batched pass (scores (n_obj,1,h,w), shared backbone taps);
    the reference loops over objects in Python (model/tracker.py:200-204);
@@ -222,7 +223,7 @@ class SegNetwork(nn.Module):
             if self.training or torch.is_grad_enabled():
                 raise RuntimeError('SegNetwork.forward on the GPU is the inference path (HIP kernels, no autograd): call it in eval() mode '
                                    'under torch.no_grad(); for training / gradients call forward_torch(...) explicitly '
-                                   '(the PyTorch definition of the same network)')
+                                   '(the PyTorch definition of the same network) or forward_train(...) (HIP kernels with autograd)')
             if self.use_graphs:
                 return self._forward_graphed(scores, features, image_size)
             # launched kernel by kernel: the deep pyramid levels still run on the shared side stream next to the 120x214 level (round 6:
@@ -248,6 +249,14 @@ class SegNetwork(nn.Module):
             h = self.CAB[L](pool if x is None else x, h)
             x = self.RRB2[L](h)
         return self.project(x, image_size)
+
+    def forward_train(self, scores, features, image_size):
+        """The training pass on the HIP kernels (model/refiner_train.py): logits (N,1,H,W) equal to forward_torch(...) for the same module
+        state, with a grad_fn whose backward writes (accumulates) .grad of every refiner parameter that requires grad.  BatchNorm uses
+        batch statistics and updates the running ones in train mode, the running statistics in eval mode.  One object per frame
+        (scores (N,1,h,w), taps (N,C,H,W)); the compat head only; no gradient into scores or taps (they must not require grad)."""
+        from .refiner_train import forward_train
+        return forward_train(self, scores, features, image_size)
 
     # ------------------------------------------------------------------------------------------------------
     # HIP path

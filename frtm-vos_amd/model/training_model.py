@@ -10,8 +10,9 @@ the target model is fitted on the augmented first frame and its two weight tenso
                      path (augmenter -> trunk -> Discriminator.init) and stores it; ``scores`` evaluates all of them on a feature batch.
   TrainerModel       the nn.Module the training driver calls (reference interface: constructor arguments, ``forward(images, labels,
                      meta) -> stats dict``, refiner-only checkpoints under the 'refiner.' prefix): per sample set, frame 0 goes to the bank,
-                     every later frame contributes one BCE backward pass through the refiner's PyTorch definition
-                     (``SegNetwork.forward_torch``: the HIP inference path of the refiner has no autograd and refuses grad mode).
+                     every later frame contributes one BCE backward pass through the refiner: its PyTorch definition
+                     (``SegNetwork.forward_torch``, the default) or, with ``refiner_backend='hip'``, its HIP training pass
+                     (``SegNetwork.forward_train``: forward and backward on the project's kernels).
 
 The training DRIVER (optimiser, schedule, data loaders, logging: train.py, lib/training.py) is out of scope.
 """
@@ -135,8 +136,14 @@ def mask_iou(pred, gt):
 
 class TrainerModel(nn.Module):
 
-    def __init__(self, augmenter, feature_extractor, disc_params, seg_network, batch_size=0, tmodel_cache=None, device=None):
+    def __init__(self, augmenter, feature_extractor, disc_params, seg_network, batch_size=0, tmodel_cache=None, device=None,
+                 refiner_backend='torch'):
+        """refiner_backend: 'torch' runs the refiner's training pass through its PyTorch definition (forward_torch), 'hip' through
+        SegNetwork.forward_train (HIP kernels forward and backward)."""
+        if refiner_backend not in ('torch', 'hip'):
+            raise ValueError("refiner_backend must be 'torch' or 'hip', not %r" % (refiner_backend,))
         super().__init__()
+        self.refiner_backend = refiner_backend
         self.augmenter = augmenter
         self.feature_extractor = feature_extractor
         self.refiner = seg_network
@@ -170,7 +177,10 @@ class TrainerModel(nn.Module):
             scores = self.bank.scores(taps[self.bank.layer])
             taps = {k: v.clone() for k, v in taps.items()}        # (the extractor may reuse its output buffers)
         with torch.enable_grad():
-            logits = self.refiner.forward_torch(scores, taps, image.shape)
+            if self.refiner_backend == 'hip':
+                logits = self.refiner.forward_train(scores, taps, image.shape)
+            else:
+                logits = self.refiner.forward_torch(scores, taps, image.shape)
             return torch.sigmoid(interpolate(logits, image.shape[-2:]))
 
     def forward(self, images, labels, meta):

@@ -159,3 +159,91 @@ def track_merge(logits, frames, n_obj, masks, labels=None, lut=None, single_obje
     H.call('frtm_track_merge', H.ptr(logits), frames, n_obj, Hh * Ww, H.ptr(masks), None if labels is None else labels.data_ptr(),
            None if lut is None else lut.data_ptr(), int(bool(single_object)), None if counts is None else counts.data_ptr(), float(thr))
     return masks
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# Refiner training (csrc/refiner_train.hip; model/refiner_train.py)
+# ----------------------------------------------------------------------------------------------------------------------
+def conv_wgrad(dy, x, k, weight=True, bias=True):
+    """Gradients of a stride-1, pad-k//2 conv (k = 1 or 3) from its output gradient dy (B,Cout,H,W) and input x (B,Cin,H,W):
+    (dW (Cout,Cin,k,k) or None, dbias (Cout) or None).  Deterministic: fixed-order sums, no atomics."""
+    B, Cout, Hh, Ww = dy.shape
+    Cin = x.shape[1]
+    assert tuple(x.shape) == (B, Cin, Hh, Ww) and (weight or bias)
+    elems = H.lib().frtm_conv_wgrad_ws_elems(B, Cout, Cin, k, Hh, Ww)
+    # its own slab buffer: growing the shared conv workspace would change the split-K factor frtm_conv2d picks for later convs
+    ws = torch.empty(elems, device=dy.device)
+    dw = torch.empty(Cout, Cin, k, k, device=dy.device) if weight else None
+    db = torch.empty(Cout, device=dy.device) if bias else None
+    H.call('frtm_conv_wgrad', H.ptr(dy), H.ptr(x), B, Cout, Cin, k, Hh, Ww, H.ptr(dw), H.ptr(db), H.ptr(ws), ws.numel())
+    return dw, db
+
+
+def bn_stats(x, running_mean, running_var, eps, factor, train):
+    """Per-channel (mean, 1/sqrt(var + eps)) of x (N,C,H,W): batch statistics when ``train`` (the running ones updated in place with
+    ``factor`` unless they are None or factor is 0), else the running statistics."""
+    N, C, Hh, Ww = x.shape
+    mean = torch.empty(C, device=x.device)
+    invstd = torch.empty(C, device=x.device)
+    part = torch.empty(2 * N * C, device=x.device, dtype=torch.float64) if train else None
+    H.call('frtm_bn_stats', H.ptr(x), N, C, Hh * Ww, float(eps), float(factor), int(bool(train)), H.ptr(running_mean), H.ptr(running_var),
+           H.ptr(mean), H.ptr(invstd), H.ptr(part))
+    return mean, invstd
+
+
+def bn_apply_relu(x, mean, invstd, gamma, beta):
+    N, C, Hh, Ww = x.shape
+    out = torch.empty_like(x)
+    H.call('frtm_bn_apply_relu', H.ptr(x), H.ptr(mean), H.ptr(invstd), H.ptr(gamma), H.ptr(beta), N, C, Hh * Ww, H.ptr(out))
+    return out
+
+
+def bn_relu_backward(dy, out, x, mean, invstd, gamma, train, affine=True):
+    """Backward of relu(batch_norm(x)) from the saved output: (dx, dgamma, dbeta); the last two None unless ``affine``."""
+    N, C, Hh, Ww = x.shape
+    dx = torch.empty_like(x)
+    dg = torch.empty(C, device=x.device) if affine else None
+    db = torch.empty(C, device=x.device) if affine else None
+    part = torch.empty(2 * N * C, device=x.device, dtype=torch.float64)
+    H.call('frtm_bn_relu_backward', H.ptr(dy), H.ptr(out), H.ptr(x), H.ptr(mean), H.ptr(invstd), H.ptr(gamma), N, C, Hh * Ww, int(bool(train)),
+           H.ptr(dx), H.ptr(dg), H.ptr(db), H.ptr(part))
+    return dx, dg, db
+
+
+def relu_backward(dy, y, out=None):
+    out = torch.empty_like(dy) if out is None else out
+    H.call('frtm_relu_backward', H.ptr(dy), H.ptr(y), dy.numel(), H.ptr(out))
+    return out
+
+
+def pyrup2x_backward(dout):
+    """Transpose of frtm_pyrup2x: (N,C,2h,2w) -> (N,C,h,w)."""
+    N, C, H2, W2 = dout.shape
+    h, w = H2 // 2, W2 // 2
+    tmp = torch.empty(N * C * H2 * w, device=dout.device)
+    din = torch.empty(N, C, h, w, device=dout.device)
+    H.call('frtm_pyrup2x_backward', H.ptr(dout), N * C, h, w, H.ptr(din), H.ptr(tmp))
+    return din
+
+
+def bilinear_backward(dout, h, w):
+    """Transpose of frtm_bilinear_resize (h,w) -> dout's size: (N,C,Ho,Wo) -> (N,C,h,w)."""
+    N, C, Ho, Wo = dout.shape
+    tmp = torch.empty(N * C * Ho * w, device=dout.device)
+    din = torch.empty(N, C, h, w, device=dout.device)
+    H.call('frtm_bilinear_backward', H.ptr(dout), N * C, h, w, Ho, Wo, H.ptr(din), H.ptr(tmp))
+    return din
+
+
+def bilinear_resize(x, size):
+    N, C, h, w = x.shape
+    out = torch.empty(N, C, int(size[0]), int(size[1]), device=x.device)
+    H.call('frtm_bilinear_resize', H.ptr(x), N * C, h, w, H.ptr(out), int(size[0]), int(size[1]))
+    return out
+
+
+def add_plane_(x, v, scale):
+    """x[n, c] += v[n, c] * scale for every pixel (in place)."""
+    N, C, Hh, Ww = x.shape
+    H.call('frtm_add_plane', H.ptr(x), H.ptr(v), float(scale), N * C, Hh * Ww)
+    return x

@@ -477,6 +477,48 @@ int frtm_project_tail_bicubic(const float* y, int n, int C, int h, int w, const 
 int frtm_plane_mean(const float* in, int planes, int HW, float* out, frtm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Refiner training (SegNetwork.forward_train, model/refiner_train.py): train-mode BatchNorm and the backward pass.
+ * No atomics: every reduction runs in a fixed order, so repeated backward passes are bitwise identical.
+ * ------------------------------------------------------------------------------------------ */
+/* Weight gradient of a stride-1, pad-k/2 conv (k = 1 or 3): dw (Cout,Cin,k,k) = sum over (n,y,x) of dy (B,Cout,H,W) times the
+ * shifted x (B,Cin,H,W); dbias (Cout) = sum of dy.  Either output may be NULL (not both).  fp32 MFMA over pixel chunks into
+ * ws (>= frtm_conv_wgrad_ws_elems floats), then an fp64 fixed-order sum of the chunks. */
+size_t frtm_conv_wgrad_ws_elems(int B, int Cout, int Cin, int k, int H, int W);
+int frtm_conv_wgrad(const float* dy, const float* x, int B, int Cout, int Cin, int k, int H, int W, float* dw, float* dbias, float* ws,
+                    size_t ws_elems, frtm_stream_t stream);
+/* BatchNorm2d statistics of x (N,C,HW).  train = 1: batch mean and 1/sqrt(biased var + eps) -> mean, invstd; when rmean / rvar are
+ * given, they are updated as nn.BatchNorm2d does with factor = momentum (or 1/num_batches_tracked for momentum=None; 0: no update),
+ * unbiased variance.  part: >= 2*N*C doubles.  train = 0: mean = rmean, invstd = 1/sqrt(rvar + eps) (part unused). */
+int frtm_bn_stats(const float* x, int N, int C, int HW, float eps, float factor, int train, float* rmean, float* rvar, float* mean,
+                  float* invstd, double* part, frtm_stream_t stream);
+/* out = relu((x - mean[c]) * invstd[c] * gamma[c] + beta[c]) */
+int frtm_bn_apply_relu(const float* x, const float* mean, const float* invstd, const float* gamma, const float* beta, int N, int C, int HW,
+                       float* out, frtm_stream_t stream);
+/* Backward of frtm_bn_apply_relu: g = dy * (out > 0); train: dx = gamma*invstd/n * (n g - sum g - xhat sum g xhat) (in fp64, one rounding), eval: dx =
+ * gamma*invstd*g; dgamma = sum g xhat, dbeta = sum g (either may be NULL).  part: >= 2*N*C doubles. */
+int frtm_bn_relu_backward(const float* dy, const float* out, const float* x, const float* mean, const float* invstd, const float* gamma,
+                          int N, int C, int HW, int train, float* dx, float* dgamma, float* dbeta, double* part, frtm_stream_t stream);
+/* dx = y > 0 ? dy : 0 for n elements (ReLU backward from the saved output; dx may alias dy) */
+int frtm_relu_backward(const float* dy, const float* y, size_t n, float* dx, frtm_stream_t stream);
+/* Transpose of frtm_pyrup2x: dout (planes,2h,2w) -> din (planes,h,w); tmp: planes*2h*w floats */
+int frtm_pyrup2x_backward(const float* dout, int planes, int h, int w, float* din, float* tmp, frtm_stream_t stream);
+/* Transpose of frtm_bilinear_resize (h,w) -> (H,W): dout (planes,H,W) -> din (planes,h,w); tmp: planes*H*w floats */
+int frtm_bilinear_backward(const float* dout, int planes, int h, int w, int H, int W, float* din, float* tmp, frtm_stream_t stream);
+/* CAB backward, per plane of dout / shallow (planes,HW): a = sum dout*shallow, b = sum dout */
+int frtm_cab_backward_reduce(const float* dout, const float* shallow, int planes, int HW, float* a, float* b, frtm_stream_t stream);
+/* Backward of frtm_cab_gate and the sigmoid: dg = a * sig'(gate); W1 (oc,2oc), W2 (oc,oc) in the conv layout [out][in]; sp, dp, gate, a
+ * (n,oc).  Writes dW1, db1, dW2, db2 (each may be NULL), dsp and ddp (n,oc); badd (n,oc) or NULL is added to ddp. */
+int frtm_cab_gate_backward(const float* sp, const float* dp, const float* gate, const float* a, const float* badd, const float* W1,
+                           const float* b1, const float* W2, int n, int oc, float* dW1, float* db1, float* dW2, float* db2, float* dsp,
+                           float* ddp, frtm_stream_t stream);
+/* ds = dout * sigmoid(gate[plane]) + dsp[plane] / HW */
+int frtm_cab_backward_shallow(const float* dout, const float* gate, const float* dsp, int planes, int HW, float* ds, frtm_stream_t stream);
+/* x[plane] += v[plane] * scale */
+int frtm_add_plane(float* x, const float* v, float scale, int planes, int HW, frtm_stream_t stream);
+/* out (n,9,H,W): out[n,t,y,x] = dl[n,0,y-ky+1,x-kx+1], t = 3ky+kx, 0 outside (the input gradient of a 3x3 conv's nine taps) */
+int frtm_shift9(const float* dl, int n, int H, int W, float* out, frtm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Affine warp of C planes (replaces lib/_npp/nppig.cpp:48-104 = NVIDIA NPP nppiWarpAffine_*, called from
  * lib/image.py:53).  fwd6_host: HOST float[6], the forward 2x3 transform (source -> destination), as
  * cv2.warpAffine / NPP take it.  mode: 0 nearest, 1 bilinear, 2 bicubic.  Outside pixels become 0.
