@@ -9,7 +9,13 @@ is the reference's own definition of FPS (model/tracker.py:130,159-161): N frame
 sequence loop, initialize() included, with a device sync on both sides.
 
     python bench.py --gpus 1 --steps 64 --warmup 8
+    python bench.py --gpus 1 --steps 64 --warmup 8 --full     # + the add-on legs after the headline (N = 1 only)
     python bench.py --gpus 8 ...            # starts 8 ranks itself (torch.distributed.run, one process per GPU)
+
+A plain run sets up, warms up, runs the timed repeats, writes --dump-outputs if asked and prints the line.  Everything else it can
+measure runs only with --full, after the headline is complete: the initialize() sweep, the dataset leg, the streaming leg, the CG
+roofline, the dominant kernel alone, the CPU oracle baseline and the dataset-level J&F against fixture G14 (the --no-<leg> options skip
+single legs of it).
 
 Workload = BASELINE.json configs[2] stand-in ("ResNet101 full-iteration optimizer, dv2017val multi-object"):
 one "dv2017-like" synthetic sequence per rank, 480x854, 2 objects (the DAVIS-2017 val mean), memory 80, c=96.
@@ -70,6 +76,10 @@ def parse(argv=None):
     ap.add_argument('--no-persistent-cg', action='store_true', help='filter re-solves as 4 launches per CG iteration instead of one persistent launch')
     ap.add_argument('--random-refiner', action='store_true',
                     help='default-initialised refiner (round-1 workload: no mask ever exceeds 0.5, updates early-out; counters are reported, not asserted)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, run the add-on legs as well (N = 1 only): initialize() sweep, dataset leg, streaming leg, '
+                         'CG roofline, dominant kernel, CPU baseline, dataset-level J&F.  The --no-<leg>, --cpu-frames, --init-sweep-counts, '
+                         '--jf-draws and --no-oracle-spread options below act on these legs only')
     ap.add_argument('--no-oracle-spread', action='store_true', help='skip the second (untimed) oracle run that measures the oracle against itself')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-streaming', action='store_true', help='skip the streaming leg (Tracker.track frame by frame: what an online caller gets)')
@@ -1192,9 +1202,9 @@ def main():
     if shard is not None:
         out['shard_rank0'] = shard
         out['frames_total'] = n_total
-    if rank == 0 and world == 1:
+    _phase('timed sequence and checks done')
+    if args.full and rank == 0 and world == 1:
         aug_cpu = [(a.cpu(), b.cpu()) for a, b in aug_log]
-        _phase('timed sequence and checks done')
         # The legs below ADD to the line; the headline above is complete without them.  One of them failing (a fixture missing, the host out
         # of memory for the evaluation pool, ...) is reported in the line under "leg_errors" instead of costing the driver the whole line.
         leg_errors = {}

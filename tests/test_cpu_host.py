@@ -314,6 +314,16 @@ def test_bench_launches_its_own_ranks_gloo(tmp_path):
     assert bad.returncode != 0 and 'WORLD_SIZE' in bad.stderr
 
 
+def test_bench_add_on_legs_are_opt_in():
+    """A plain `bench.py` run is the headline alone; the add-on legs (CPU baseline, J&F vs fixture, CG roofline, ...) need --full."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location('bench_mod', os.path.join(ROOT, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    assert bench.parse(['--gpus', '1', '--steps', '64', '--warmup', '8']).full is False
+    assert bench.parse(['--full', '--no-cpu-baseline']).full is True
+
+
 def test_bench_sharded_mode_cuts_the_dataset_over_the_ranks_gloo(tmp_path):
     """`python bench.py --gpus 2 --sequences 11` (BASELINE config 4's shape: one dataset sharded over the ranks, strong scaling): the two
     ranks take disjoint, length-balanced shares that cover the dataset; rank 0 reports the SUM of frames over the max wall time."""

@@ -2,7 +2,7 @@
 # queue of its own against an arbitrary pool stream (FRTM_COPY_STREAM_PROBE=0)
 cd $GRAFT_REPO_ROOT; O=gpurun_out/streams; mkdir -p $O
 for r in 1 2 3; do for v in 1 0; do
-  FRTM_COPY_STREAM_PROBE=$v python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-cg-roofline --no-streaming --no-init-sweep --no-jf-fixture --repeats 1 2>/dev/null > $O/d.json
+  FRTM_COPY_STREAM_PROBE=$v python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-cg-roofline --no-streaming --no-init-sweep --no-jf-fixture --repeats 1 2>/dev/null > $O/d.json
   python - <<PY
 import json
 d = json.loads(open('$O/d.json').read().strip().splitlines()[-1])

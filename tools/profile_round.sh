@@ -7,8 +7,8 @@ mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 # 1. the bench line of the default run (64 frames) and of the driver's run (20 frames), no profiler
-python $R/bench.py --steps 64 --warmup 8 --no-cpu-baseline > $O/bench64.json 2> $O/bench64.err
-python $R/bench.py --steps 20 --warmup 5 > $O/bench20.json 2> $O/bench20.err
+python $R/bench.py --full --steps 64 --warmup 8 --no-cpu-baseline > $O/bench64.json 2> $O/bench64.err
+python $R/bench.py --full --steps 20 --warmup 5 > $O/bench20.json 2> $O/bench20.err
 # 2. kernel trace + stats of the same default command
 rm -rf /tmp/prof_final
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_final -o prof -- python $R/bench.py --no-cpu-baseline --no-init-sweep --no-cg-roofline --no-dataset-sim --no-streaming --repeats 1 > $O/bench_traced.json 2>/dev/null

@@ -3,8 +3,8 @@
 cd $GRAFT_REPO_ROOT; O=gpurun_out/r4final; mkdir -p $O
 ( time timeout 900 python -m pytest tests -q -m gpu --durations=8 ) > $O/pytest.log 2>&1
 tail -4 $O/pytest.log
-( time timeout 400 python bench.py --steps 20 --warmup 5 ) > $O/bench20.json 2> $O/bench20.err
-( time timeout 400 python bench.py --steps 64 --warmup 8 --no-cpu-baseline ) > $O/bench64.json 2> $O/bench64.err
+( time timeout 400 python bench.py --full --steps 20 --warmup 5 ) > $O/bench20.json 2> $O/bench20.err
+( time timeout 400 python bench.py --full --steps 64 --warmup 8 --no-cpu-baseline ) > $O/bench64.json 2> $O/bench64.err
 cd /tmp && export TMPDIR=/tmp; R=$GRAFT_REPO_ROOT
 rm -rf /tmp/prof_final
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_final -o prof -- python $R/bench.py --no-cpu-baseline --no-init-sweep --no-cg-roofline --no-dataset-sim --no-streaming --no-jf-fixture --repeats 1 > $R/$O/bench_traced.json 2>/dev/null
