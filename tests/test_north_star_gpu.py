@@ -95,14 +95,51 @@ def _clone_disc(od, dtype):
     return d
 
 
-def _teacher_forced(size, n_frames, n_obj, seed, disc):
+def cpu_threads():
+    """Threads for the CPU oracle: OMP_NUM_THREADS (the CPUs a command may use), at most 16 -- os.cpu_count() counts the whole machine."""
+    try:
+        n = int(os.environ.get('OMP_NUM_THREADS', '').split(',')[0])
+    except ValueError:
+        n = os.cpu_count() or 1
+    return max(1, min(16, n))
+
+
+def _first_frame_fits(trk, cpu, new):
+    # the first-frame fits themselves are 45 CG iterations each: they amplify the 2e-4 difference between the two trunks (the fp64
+    # arbiter below measures 10 % rms between the float32 and float64 runs of the SAME fit); here only that they land in the same place
+    for oid in new:
+        hd, od = trk.targets[oid].discriminator, cpu.targets[oid]['d']
+        e2, e1 = rms(hd.filter.weight, od.w2) / rms(od.w2, 0 * od.w2), rms(hd.project.weight, od.w1) / rms(od.w1, 0 * od.w1)
+        print('first-frame fit, object %d: HIP vs fp32 oracle rms relative filter %.3f, projection %.3f' % (oid, e2, e1))
+        assert e2 < 0.3 and e1 < 0.3
+
+
+def _hip_state(hd):
+    """What a frame must not change in a target model that is not updated on it (host copies)."""
+    m = hd.memory
+    n = m.current_size
+    return dict(project=hd.project.weight.cpu().clone(), filter=hd.filter.weight.cpu().clone(), samples=m.samples[:n].cpu().clone(),
+                weights=m.weights.cpu().clone(), normal_B=m.normal_B[:n].cpu().clone(), normal_c=m.normal_c[:n].cpu().clone(),
+                size=n, prev=m.previous_replace_ind, inserts=m.insert_counts, frame_num=hd.frame_num)
+
+
+def _teacher_forced(size, n_frames, n_obj, seed, disc, late_object_at=None, check=None, threads=None):
     """Teacher-forced comparison of Tracker.track() with oracle/tracker_ref.py: before every frame the oracle's state is copied into the HIP
-    target models, both sides then track that ONE frame.  Returns the worst deviations over the run."""
+    target models, both sides then track that ONE frame.  Returns the worst deviations over the run.
+
+    ``late_object_at``: the sequence's last object starts on that frame (SyntheticSequence).  On its entry frame the old objects' state is
+    forced, both sides run initialize() for the new object (same start weights, same augmentation), then track() for the old ones (reference
+    tracker.py:136-141).  Checked there: initialize() left the same planes as the oracle's (old planes zeroed, the new one = its label mask),
+    object-to-plane order and plane count, the new object's first-frame fit, its plane before the merge = its label mask exactly, and its
+    target model untouched by the frame (reference :200-204, :223-225: it is neither classified nor updated on its start frame); the entry
+    frame's gates go into worst['entry_*'].  ``check(t, trk, cpu, solved)``: called after every tracked frame (``solved``: ids that re-solved).
+    ``threads``: the oracle's CPU threads.  The default stays what the 480p and 720p gates were measured with: the oracle's rounding depends on
+    its thread count, and the headline test's single-re-solve arbiter (bound 1.5) measured 1.524 with 16 threads instead of 32."""
     from frtm_vos_amd.lib.synthetic import SyntheticSequence
     torch.set_grad_enabled(False)
-    torch.set_num_threads(min(32, os.cpu_count()))
+    torch.set_num_threads(threads or min(32, os.cpu_count()))
     every = disc['train_skipping']
-    seq = SyntheticSequence('tf', n_frames, size, n_obj, seed=seed)
+    seq = SyntheticSequence('tf', n_frames, size, n_obj, seed=seed, late_object_at=late_object_at)
     refiner = JF.refiner_for('resnet101')
     over = {k: v for k, v in disc.items() if JF.DISC.get(k) != v}
     trk = _hip_tracker('resnet101', refiner, **over)
@@ -115,28 +152,50 @@ def _teacher_forced(size, n_frames, n_obj, seed, disc):
     trk.current_frame, trk.targets = 0, dict()
     trk.initialize(image.to(DEV), labels.to(DEV), new)
     cpu.initialize(image, labels, new)
-    # the first-frame fits themselves are 45 CG iterations each: they amplify the 2e-4 difference between the two trunks (the fp64
-    # arbiter below measures 10 % rms between the float32 and float64 runs of the SAME fit); here only that they land in the same place
-    for oid in new:
-        hd, od = trk.targets[oid].discriminator, cpu.targets[oid]['d']
-        e2, e1 = rms(hd.filter.weight, od.w2) / rms(od.w2, 0 * od.w2), rms(hd.project.weight, od.w1) / rms(od.w1, 0 * od.w1)
-        print('first-frame fit, object %d: HIP vs fp32 oracle rms relative filter %.3f, projection %.3f' % (oid, e2, e1))
-        assert e2 < 0.3 and e1 < 0.3
+    _first_frame_fits(trk, cpu, new)
     trk.current_frame, cpu.current_frame = 1, 1
     trk._raw_log = []
     worst = dict(raw=0.0, merged=0.0, filt=0.0, filt_solve=0.0, sw=0.0, flips=0, arb=0.0, arb_pooled=0.0)
     pool_h, pool_o = [], []
     for t in range(1, n_frames):
-        for oid in new:
+        image, labels, new = seq[t]
+        old = [oid for oid, ct in cpu.targets.items() if ct['start'] < t]
+        for oid in old:
             _force_state(trk.targets[oid].discriminator, cpu.targets[oid]['d'])
-        trk.current_masks.copy_(cpu.current_masks.float())
-        image = seq[t][0]
-        will_solve = (cpu.targets[new[0]]['d'].frame_num + 1) % every == 0
-        d64 = {oid: _clone_disc(cpu.targets[oid]['d'], torch.float64) for oid in new} if will_solve else {}
+        if new:
+            # reference tracker.py:136-141: initialize() for the objects that start here, then track() for the old ones
+            trk.initialize(image.to(DEV), labels.to(DEV), new)
+            cpu.initialize(image, labels, new)
+            assert torch.equal(trk.current_masks.cpu(), cpu.current_masks.float()), t        # old planes zeroed, new plane = label mask
+            assert list(trk.targets) == list(cpu.targets), (list(trk.targets), list(cpu.targets))
+            assert [h.index for h in trk.targets.values()] == [c['index'] for c in cpu.targets.values()], t
+            _first_frame_fits(trk, cpu, new)
+            fresh = {oid: _hip_state(trk.targets[oid].discriminator) for oid in new}
+        else:
+            trk.current_masks.copy_(cpu.current_masks.float())
+        will = [oid for oid in old if (cpu.targets[oid]['d'].frame_num + 1) % every == 0]
+        d64 = {oid: _clone_disc(cpu.targets[oid]['d'], torch.float64) for oid in will}
         trk.track(image.to(DEV))
         cpu.track(image)
         raw_h, raw_c = trk._raw_log[-1][1].cpu(), cpu.raw_masks
+        assert raw_h.shape == raw_c.shape and trk.current_masks.shape == cpu.current_masks.shape, (t, raw_h.shape, raw_c.shape)
         e_raw = float((raw_h[1:] - raw_c[1:]).abs().max())
+        for oid in new:
+            # the new object's plane before the merge is its start mask on both sides (reference :188, not overwritten by :200-204)
+            k, mask = cpu.targets[oid]['index'], cpu.targets[oid]['mask'].reshape(raw_c.shape[-2:]).float()
+            assert torch.equal(raw_c[k], mask) and torch.equal(raw_h[k], mask), (t, oid)
+            # ... and its target model is neither scored nor updated on this frame: memory, filter, projection, counters as initialize() left them
+            now, was = _hip_state(trk.targets[oid].discriminator), fresh[oid]
+            for key, v in was.items():
+                assert (torch.equal(now[key], v) if torch.is_tensor(v) else now[key] == v), (t, oid, key)
+            assert cpu.targets[oid]['d'].frame_num == 0 and cpu.targets[oid]['d'].memory.current_size == was['size'], (t, oid)
+        if new and old:
+            # (1 - start mask) products of the old objects' planes (reference :206-212): zero wherever the new object's mask is set
+            for oid in old:
+                k = cpu.targets[oid]['index']
+                inside = sum(cpu.targets[n]['mask'].reshape(raw_c.shape[-2:]) for n in new) > 0
+                assert float(raw_h[k][inside].abs().max()) == 0.0 and float(raw_c[k][inside].abs().max()) == 0.0, (t, oid, e_raw)
+            worst['entry_raw'] = e_raw
         # merged masks: the merge contains an arg-max (tracker.py:217-221); a pixel whose two best classes are closer than the tolerance
         # may flip, and the mask value jumps with it.  Those pixels are counted, not compared.
         p = torch.clamp(raw_c, 1e-7, 1 - 1e-7)
@@ -148,9 +207,10 @@ def _teacher_forced(size, n_frames, n_obj, seed, disc):
         flips = int((~stable).sum())
         worst['flips'] = max(worst['flips'], flips)
         assert flips < 2e-3 * stable.numel(), (t, flips)
-        solve = cpu.targets[new[0]]['d'].frame_num % every == 0
-        for oid in new:
+        solved = [oid for oid in old if cpu.targets[oid]['d'].frame_num % every == 0]
+        for oid in old:
             hd, od = trk.targets[oid].discriminator, cpu.targets[oid]['d']
+            solve = oid in solved
             e_f = relmax(hd.filter.weight, od.w2)
             worst['filt_solve' if solve else 'filt'] = max(worst['filt_solve' if solve else 'filt'], e_f)
             if solve:
@@ -171,8 +231,13 @@ def _teacher_forced(size, n_frames, n_obj, seed, disc):
             assert hd.memory.previous_replace_ind == od.memory.prev_ind, (t, oid)
             worst['sw'] = max(worst['sw'], float((hd.memory.weights.cpu() - od.memory.weights).abs().max()))
         worst['raw'], worst['merged'] = max(worst['raw'], e_raw), max(worst['merged'], e_mrg)
-        print('frame %2d%s: max |mask diff| before merge %.2e, merged (stable pixels) %.2e, %d unstable pixels' %
-              (t, ' (re-solve)' if solve else '', e_raw, e_mrg, flips), flush=True)
+        if new and old:
+            worst['entry_merged'] = e_mrg
+        print('frame %2d%s%s: max |mask diff| before merge %.2e, merged (stable pixels) %.2e, %d unstable pixels' %
+              (t, ' (re-solve%s)' % ('' if len(solved) == len(old) else ' of %s' % solved) if solved else '',
+               ' (object %s enters)' % new if new else '', e_raw, e_mrg, flips), flush=True)
+        if check is not None:
+            check(t, trk, cpu, solved)
         trk.current_frame += 1
         cpu.current_frame += 1
     if pool_h:          # all re-solves of the run together: rms of the distances to float64, HIP over float32 oracle
@@ -251,42 +316,127 @@ def test_fp64_arbiter_update_problem_full_memory():
             assert e_h <= 1.5 * e_o + 1e-6 * scale, (persistent, k, e_h, e_o)
 
 
-def test_fp64_arbiter_joint_first_frame_fit():
-    """The joint (project, filter) fit of Discriminator.init (discriminator.py:165-176) at Cin = 1024, K = 5, 30x54 / 480x854 through the
-    full (5,10,10,10,10) schedule = 45 CG iterations."""
-    from test_oracle_golden import _joint_inputs
+def _oracle_joint_fit(dtype, X, Y, w1, w2, iters):
+    K = X.shape[0]
+    mem = O.MemoryRef(K, X.shape[1:], Y.shape[1:], 0.1, dtype)
+    mem.initialize(X.to(dtype), Y.to(dtype), O.pixel_weights(Y.to(dtype), PW, dtype))
+    a, b = w1.clone().to(dtype), w2.clone().to(dtype)
+    O.GaussNewtonCGRef(O.InitProblemRef(mem, (1e-4, 1e-2), (1e-4, 1e-2)), [a, b], fletcher_reeves=False,
+                       direction_forget_factor=0.9 ** 750).run(iters)
+    return a, b
+
+
+def _hip_joint_fit(composed, X, Y, w1, w2, iters):
+    """The joint fit on the HIP path from the same start: returns (problem, solver, project weight, filter weight)."""
     from frtm_vos_amd.model.discriminator import DiscriminatorLoss
     from frtm_vos_amd.model.memory import Memory
     from frtm_vos_amd.model.optimizer import GaussNewtonCG
     from frtm_vos_amd.lib.tensorlist import TensorList
+    K, cin, h, w = X.shape
+    mem = Memory(K, (cin, h, w), tuple(Y.shape[1:]), DEV, 0.1, pixel_weighting=PW)
+    mem.initialize(X.to(DEV), Y.to(torch.uint8).to(DEV))
+    w1d = torch.nn.Parameter(w1.clone().to(DEV), requires_grad=False)
+    w2d = torch.nn.Parameter(w2.clone().to(DEV), requires_grad=False)
+    prob = DiscriminatorLoss(mem, (1e-4, 1e-2), (1e-4, 1e-2), w2d, w1d)
+    prob.composed = composed
+    opt = GaussNewtonCG(prob, TensorList([w1d, w2d]), fletcher_reeves=False, standard_alpha=True, direction_forget_factor=0.9 ** 750)
+    opt.run(iters)
+    return prob, opt, w1d, w2d
+
+
+def test_fp64_arbiter_joint_first_frame_fit():
+    """The joint (project, filter) fit of Discriminator.init (discriminator.py:165-176) at Cin = 1024, K = 5, 30x54 / 480x854 through the
+    full (5,10,10,10,10) schedule = 45 CG iterations."""
+    from test_oracle_golden import _joint_inputs
     torch.set_num_threads(min(32, os.cpu_count()))
     K, cin, c, h, w, H, W = 5, 1024, 96, 30, 54, 480, 854
     X, Y, w1, w2, _, _, _ = _joint_inputs(77, K, cin, c, h, w, H, W)
     iters = (5, 10, 10, 10, 10)
-
-    def oracle(dtype):
-        mem = O.MemoryRef(K, X.shape[1:], Y.shape[1:], 0.1, dtype)
-        mem.initialize(X.to(dtype), Y.to(dtype), O.pixel_weights(Y.to(dtype), PW, dtype))
-        a, b = w1.clone().to(dtype), w2.clone().to(dtype)
-        O.GaussNewtonCGRef(O.InitProblemRef(mem, (1e-4, 1e-2), (1e-4, 1e-2)), [a, b], fletcher_reeves=False,
-                           direction_forget_factor=0.9 ** 750).run(iters)
-        return a, b
-    a64, b64 = oracle(torch.float64)
-    a32, b32 = oracle(torch.float32)
+    a64, b64 = _oracle_joint_fit(torch.float64, X, Y, w1, w2, iters)
+    a32, b32 = _oracle_joint_fit(torch.float32, X, Y, w1, w2, iters)
     for composed in (True, False):
-        mem = Memory(K, (cin, h, w), (1, H, W), DEV, 0.1, pixel_weighting=PW)
-        mem.initialize(X.to(DEV), Y.to(torch.uint8).to(DEV))
-        w1d = torch.nn.Parameter(w1.clone().to(DEV), requires_grad=False)
-        w2d = torch.nn.Parameter(w2.clone().to(DEV), requires_grad=False)
-        prob = DiscriminatorLoss(mem, (1e-4, 1e-2), (1e-4, 1e-2), w2d, w1d)
-        prob.composed = composed
-        GaussNewtonCG(prob, TensorList([w1d, w2d]), fletcher_reeves=False, standard_alpha=True, direction_forget_factor=0.9 ** 750).run(iters)
+        _, _, w1d, w2d = _hip_joint_fit(composed, X, Y, w1, w2, iters)
         for name, hv, v32, v64 in (('project', w1d, a32, a64), ('filter', w2d, b32, b64)):
             e_h, e_o = rms(hv, v64), rms(v32, v64)
             scale = float(v64.pow(2).mean().sqrt())
             print('joint fit Cin=1024 (%s form), %s: rms |HIP - fp64| %.2e, |fp32 oracle - fp64| %.2e (rms of the weights %.2e)'
                   % ('composed' if composed else 'GEMM', name, e_h, e_o, scale))
             assert e_h <= 1.5 * e_o + 1e-6 * scale, (composed, name, e_h, e_o)
+
+
+def _pooled(e_h, e_o):
+    """rms over a set of distances to float64: HIP over the float32 oracle."""
+    return float(np.sqrt(np.mean(np.square(e_h))) / max(np.sqrt(np.mean(np.square(e_o))), 1e-12))
+
+
+ARB_1080P_DRAWS = (0, 1, 2)
+
+
+def test_fp64_arbiter_update_problem_1080p():
+    """The update problem at config 5's size: N = 32 (its memory), c = 96, 68x120 / 1080x1920, run((10,)) twice with the carried CG state.
+    The persistent CG launch is asked for and must NOT be taken (w = 120 is wider than its plan allows): the multi-kernel chain with the strip
+    forms of csrc/wide_maps.hip runs.  One ratio of two noise magnitudes is itself noisy (the 720p teacher-forced test), so three seeded draws
+    are pooled: per draw (its two runs) <= 2.0, all draws together <= 1.5."""
+    from test_fullsize_gpu import _fullsize_inputs, _problem
+    torch.set_num_threads(cpu_threads())
+    N, c, h, w, H, W = 32, 96, 68, 120, 1080, 1920
+    t0 = time.time()
+    all_h, all_o, each = [], [], []
+    for draw in ARB_1080P_DRAWS:
+        X, Y, sw, w2, _ = _fullsize_inputs(31 + draw, N, c, h, w, H, W)
+        f64 = _oracle_update_run(torch.float64, X, Y, sw, w2, 2)
+        f32 = _oracle_update_run(torch.float32, X, Y, sw, w2, 2)
+        mem, prob, opt, wv = _problem(N, c, h, w, H, W, X, Y, sw, w2)
+        opt.persistent = True
+        assert prob.wide_parts > 0 and opt._persistent_plan() is None, (prob.wide_parts, 'the persistent CG launch must not be eligible at w = 120')
+        d_h, d_o = [], []
+        for k in range(2):
+            opt.run((10,))
+            assert not opt._persistent_launched and not opt._launched          # the chain ran, no resident launch
+            e_h, e_o = rms(wv, f64[k]), rms(f32[k], f64[k])
+            scale = float(f64[k].double().pow(2).mean().sqrt())
+            print('update problem N=32 at 1080p, draw %d, run %d (multi-kernel, %d strips): rms |HIP - fp64| %.2e, |fp32 oracle - fp64| %.2e '
+                  '(rms of the filter %.2e), ratio %.3f' % (draw, k + 1, prob.wide_parts, e_h, e_o, scale, e_h / max(e_o, 1e-12)), flush=True)
+            d_h.append(e_h)
+            d_o.append(e_o)
+        each.append(_pooled(d_h, d_o))
+        all_h += d_h
+        all_o += d_o
+    pooled = _pooled(all_h, all_o)
+    print('update problem at 1080p: ratio per draw %s, pooled over %d runs %.3f  (%.0f s)' % (['%.3f' % v for v in each], len(all_h), pooled, time.time() - t0))
+    assert max(each) <= 2.0 and pooled <= 1.5, (each, pooled)
+
+
+def test_fp64_arbiter_joint_first_frame_fit_1080p():
+    """The joint first-frame fit at config 5's size: Cin = 1024, K = 5, 68x120 / 1080x1920, the full (5,10,10,10,10) schedule, in the composed
+    and in the GEMM form.  The resident joint launch is not eligible on these maps, the strip forms are (wide_parts > 0): asserted.  Three seeded
+    draws, per form and weight: each draw <= 2.0, the draws pooled <= 1.5."""
+    from test_oracle_golden import _joint_inputs
+    torch.set_num_threads(cpu_threads())
+    K, cin, c, h, w, H, W = 5, 1024, 96, 68, 120, 1080, 1920
+    iters = (5, 10, 10, 10, 10)
+    t0 = time.time()
+    res = {}
+    for draw in ARB_1080P_DRAWS:
+        X, Y, w1, w2, _, _, _ = _joint_inputs(87 + draw, K, cin, c, h, w, H, W)
+        a64, b64 = _oracle_joint_fit(torch.float64, X, Y, w1, w2, iters)
+        a32, b32 = _oracle_joint_fit(torch.float32, X, Y, w1, w2, iters)
+        for composed in (True, False):
+            prob, opt, w1d, w2d = _hip_joint_fit(composed, X, Y, w1, w2, iters)
+            assert prob.wide_parts > 0 and prob._use_composed() == composed, (prob.wide_parts, composed)
+            assert prob.persistent_joint_args() is None and not getattr(opt, '_joint_launched', False)      # no resident joint launch
+            form = 'composed' if composed else 'GEMM'
+            for name, hv, v32, v64 in (('project', w1d, a32, a64), ('filter', w2d, b32, b64)):
+                e_h, e_o = rms(hv, v64), rms(v32, v64)
+                print('joint fit at 1080p, draw %d (%s form, %d strips), %s: rms |HIP - fp64| %.2e, |fp32 oracle - fp64| %.2e (rms of the weights %.2e), '
+                      'ratio %.3f' % (draw, form, prob.wide_parts, name, e_h, e_o, float(v64.pow(2).mean().sqrt()), e_h / max(e_o, 1e-12)), flush=True)
+                res.setdefault((form, name), []).append((e_h, e_o))
+    for (form, name), v in res.items():
+        each = [e_h / max(e_o, 1e-12) for e_h, e_o in v]
+        pooled = _pooled([e_h for e_h, _ in v], [e_o for _, e_o in v])
+        print('joint fit at 1080p, %s form, %s: ratio per draw %s, pooled %.3f' % (form, name, ['%.3f' % r for r in each], pooled))
+        assert max(each) <= 2.0 and pooled <= 1.5, (form, name, each, pooled)
+    print('(%.0f s)' % (time.time() - t0))
 
 
 def test_fp64_arbiter_free_running_masks():
