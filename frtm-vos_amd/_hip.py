@@ -132,6 +132,8 @@ SIGNATURES = {
     'frtm_aug_blend': (I, [P, P, I, I, I, P, P, P, P, P]),
     'frtm_blur2d': (I, [P, I, I, I, P, I, I, P, P]),
     'frtm_blur_gauss2d': (I, [P, I, I, I, I, F, F, F, P, P]),
+    'frtm_jf_workspace_bytes': (ctypes.c_size_t, [I, I, I, I]),
+    'frtm_jf_counts': (I, [P, P, I, I, I, I, ctypes.POINTER(I), I, I, P, P, ctypes.c_size_t, P]),
 }
 
 _lib = None

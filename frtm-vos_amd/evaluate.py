@@ -222,7 +222,7 @@ def main(argv=None):
             for measure in ('J', 'F'):
                 print()
                 print('Computing %s-scores' % measure)
-                evaluate_dataset(dset, out_path, measure=measure)
+                evaluate_dataset(dset, out_path, measure=measure, device=args.dev)
     if world > 1:
         import torch.distributed as dist
         dist.barrier()

@@ -1,5 +1,9 @@
 """J / F evaluation of label sequences held in memory (counterpart of the reference's lib/evaluation.py:9-85, which reads
-PNGs from disk).  Frames 0 and the last one are skipped like in the DAVIS protocol (lib/evaluation.py:35-41)."""
+PNGs from disk).  Frames 0 and the last one are skipped like in the DAVIS protocol (lib/evaluation.py:35-41).
+
+Label maps that are CUDA tensors (the list Tracker.run_sequence returns, or one (T,H,W) tensor) are scored on the GPU: the integer
+counts of every frame and object in one call (lib/davis.py: device_counts), one device-to-host read per sequence, the same float64
+arithmetic on the host.  numpy arrays and CPU tensors take the numpy path."""
 import numpy as np
 
 from . import davis as _davis
@@ -10,9 +14,24 @@ def evaluate_sequence(pred_labels, gt_labels, obj_ids, measure='J', skip_first_l
     """pred_labels / gt_labels: lists of (H,W) integer label images; returns {obj_id: per-frame values}."""
     fn = db_eval_iou if measure == 'J' else db_eval_boundary
     frames = range(1, len(pred_labels) - 1) if skip_first_last and len(pred_labels) > 2 else range(len(pred_labels))
+    if _davis.on_device(pred_labels, gt_labels):
+        obj_ids = list(obj_ids)
+        return _values_from_counts(_davis.device_counts(pred_labels, gt_labels, obj_ids), obj_ids, measure, frames)
     out = {}
     for oid in obj_ids:
         out[oid] = [fn(np.asarray(gt_labels[t]) == oid, np.asarray(pred_labels[t]) == oid) for t in frames]
+    return out
+
+
+def _values_from_counts(counts, obj_ids, measure, frames):
+    """{obj_id: per-frame values} from the (T,K,6) counts of davis.device_counts.  The numpy path above hands the ground truth to
+    db_eval_boundary as its first (foreground) mask; the same order here, so that the two paths run the same expressions."""
+    out = {}
+    for k, oid in enumerate(obj_ids):
+        if measure == 'J':
+            out[oid] = [_davis.iou_from_counts(int(counts[t, k, 0]), int(counts[t, k, 1])) for t in frames]
+        else:
+            out[oid] = [_davis.f_from_counts(int(counts[t, k, 3]), int(counts[t, k, 2]), int(counts[t, k, 5]), int(counts[t, k, 4])) for t in frames]
     return out
 
 
@@ -28,13 +47,15 @@ def evaluate_results(results, measure='J'):
     return dict(measure=measure, mean=m, per_sequence=per_seq)
 
 
-def evaluate_dataset(dset, results_path=None, measure='J', to_file=True):
+def evaluate_dataset(dset, results_path=None, measure='J', to_file=True, device=None):
     """The reference's call (lib/evaluation.py:9-85; driver: evaluate.py:159-165): ``dset`` yields sequences with .name / .annos /
     .obj_ids / .start_frames / .merge_objects, the tracker's PNGs are read from ``results_path``/<sequence>/<frame>.png (a Path or a
     str), per-sequence lines and the final "<measure>: mean, recall, decay" line go to stdout and results_path/evaluation-<measure>.txt.
     Returns the summary dict.  Results held in memory go through ``evaluate_results``; for backward compatibility
     ``evaluate_dataset(results)`` / ``evaluate_dataset(results, 'J')`` with a list of tuples still dispatches there -- decided by the
-    TYPE of the first argument, never by what results_path looks like (round-2 ADVICE)."""
+    TYPE of the first argument, never by what results_path looks like (round-2 ADVICE).
+    ``device``: a CUDA device scores the PNGs there (each sequence uploaded once, lib/davis.py: device_counts); the printed lines and
+    the text file are the same byte for byte.  None: numpy."""
     in_memory = isinstance(dset, (list, tuple)) and (len(dset) == 0 or isinstance(dset[0], (list, tuple)))
     if in_memory:
         if isinstance(results_path, str) and results_path in ('J', 'F'):
@@ -44,21 +65,29 @@ def evaluate_dataset(dset, results_path=None, measure='J', to_file=True):
         return evaluate_results(dset, measure)
     if results_path is None:
         raise TypeError('evaluate_dataset(dset, results_path, measure): results_path (directory of the PNGs) is required for a dataset object')
-    return _evaluate_dataset_files(dset, results_path, measure, to_file)
+    return _evaluate_dataset_files(dset, results_path, measure, to_file, device)
 
 
 def j_and_f(pred_labels, gt_labels, obj_ids):
     """Mean of J-mean and F-mean over objects, in percent (the DAVIS-2017 'J&F' number) for one sequence."""
-    j = evaluate_sequence(pred_labels, gt_labels, obj_ids, 'J')
-    f = evaluate_sequence(pred_labels, gt_labels, obj_ids, 'F')
+    if _davis.on_device(pred_labels, gt_labels):                 # both measures from one set of counts: one call, one read
+        obj_ids = list(obj_ids)
+        counts = _davis.device_counts(pred_labels, gt_labels, obj_ids)
+        frames = range(1, len(counts) - 1) if len(counts) > 2 else range(len(counts))
+        j, f = (_values_from_counts(counts, obj_ids, m, frames) for m in 'JF')
+    else:
+        j = evaluate_sequence(pred_labels, gt_labels, obj_ids, 'J')
+        f = evaluate_sequence(pred_labels, gt_labels, obj_ids, 'F')
     jm = np.mean([np.mean(v) for v in j.values()])
     fm = np.mean([np.mean(v) for v in f.values()])
     return 100.0 * (jm + fm) / 2.0, 100.0 * jm, 100.0 * fm
 
 
-def _evaluate_dataset_files(dset, results_path, measure='J', to_file=True):
+def _evaluate_dataset_files(dset, results_path, measure='J', to_file=True, device=None):
     from collections import OrderedDict as odict
     from pathlib import Path
+    import torch
+    on_gpu = device is not None and torch.device(device).type == 'cuda'
     from .image import imread
     from .utils import text_bargraph
     results_path = Path(results_path)
@@ -86,7 +115,16 @@ def _evaluate_dataset_files(dset, results_path, measure='J', to_file=True):
         assert 0 not in object_info
         n_objs = len(object_info)
         out('%d/%d: %s: %d object%s' % (j + 1, n_seqs, sequence.name, n_objs, 's' if n_objs > 1 else ''))
-        r = _davis.evaluate_sequence(segmentations, annotations, object_info, measure=measure)
+        if on_gpu and len(annotations) > 0:
+            from .. import _hip
+            dev = _hip.normalize_device(device)
+            with torch.cuda.device(dev):                            # one upload per sequence and side, then one call and one read
+                ann_d = _hip.upload(torch.stack([v.reshape(v.shape[-2:]) for v in annotations.values()]), dev)
+                seg_d = _hip.upload(torch.stack([v.reshape(v.shape[-2:]) for v in segmentations.values()]), dev)
+                counts = _davis.device_counts(seg_d, ann_d, list(object_info.keys()))
+            r = _davis.sequence_from_counts(counts, list(annotations.keys()), object_info, measure)
+        else:
+            r = _davis.evaluate_sequence(segmentations, annotations, object_info, measure=measure)
         results[sequence.name] = r
         per_obj, per_frame = [], []
         for obj_id, score in r['raw'].items():

@@ -247,3 +247,48 @@ def add_plane_(x, v, scale):
     N, C, Hh, Ww = x.shape
     H.call('frtm_add_plane', H.ptr(x), H.ptr(v), float(scale), N * C, Hh * Ww)
     return x
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# DAVIS J / F scoring (csrc/jf_eval.hip; lib/davis.py)
+# ----------------------------------------------------------------------------------------------------------------------
+JF_MAX_RADIUS = 64
+JF_WS_BUDGET = 32 << 20        # bytes of boundary bit planes per call into the library; longer sequences go in frame chunks
+
+
+def jf_counts(pred, truth, obj_ids, radius):
+    """The integer counts behind J and F (frtm_jf_counts): pred / truth (T,H,W) uint8 or int32 label maps on the GPU, ``obj_ids`` K ints,
+    ``radius`` of the matching disk in pixels (1 ... 64) -> (T,K,6) int32 device tensor = inter, union, n_fg, n_gt, fg_match, gt_match
+    per (frame, object).  Enqueued on the current stream; no host synchronisation."""
+    for name, t in (('pred', pred), ('truth', truth)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError('jf_counts: %s must be a tensor, got %s' % (name, type(t).__name__))
+        if not t.is_cuda:
+            raise RuntimeError('jf_counts: %s is on %s; the J / F kernels run on the GPU only (no CPU fallback; lib/davis.py has the '
+                               'numpy definition)' % (name, t.device))
+    if pred.device != truth.device:
+        raise ValueError('jf_counts: pred on %s, truth on %s' % (pred.device, truth.device))
+    if pred.dtype != truth.dtype or pred.dtype not in (torch.uint8, torch.int32):
+        raise TypeError('jf_counts: label maps must both be uint8 or both int32, got %s and %s' % (pred.dtype, truth.dtype))
+    if pred.dim() != 3 or pred.shape != truth.shape or pred.numel() == 0:
+        raise ValueError('jf_counts: expected two (T,H,W) label maps of one non-empty shape, got %s and %s' % (tuple(pred.shape), tuple(truth.shape)))
+    r = int(radius)
+    if not 1 <= r <= JF_MAX_RADIUS:
+        raise ValueError('jf_counts: disk radius %d outside 1 ... %d' % (r, JF_MAX_RADIUS))
+    ids = [int(i) for i in obj_ids]
+    T, Hh, Ww = pred.shape
+    K = len(ids)
+    counts = torch.empty(T, K, 6, dtype=torch.int32, device=pred.device)
+    if K == 0:
+        return counts
+    pred, truth = pred.contiguous(), truth.contiguous()
+    L = H.lib()
+    ids_c = (ctypes.c_int * K)(*ids)
+    per_frame = L.frtm_jf_workspace_bytes(1, Hh, Ww, K)
+    step = max(1, min(JF_WS_BUDGET // per_frame, 65535 // (2 * K), T))
+    ws = torch.empty(step * per_frame, dtype=torch.uint8, device=pred.device)
+    for t0 in range(0, T, step):
+        n = min(step, T - t0)
+        H.call('frtm_jf_counts', H.ptr(pred[t0:t0 + n]), H.ptr(truth[t0:t0 + n]), pred.element_size(), n, Hh, Ww, ids_c, K, r,
+               H.ptr(counts[t0:t0 + n]), H.ptr(ws), ws.numel())
+    return counts

@@ -581,6 +581,16 @@ int frtm_blur2d(const float* src, int planes, int H, int W, const float* G, int 
 int frtm_blur_gauss2d(const float* src, int planes, int H, int W, int half, float qa, float qb, float qc, float* dst,
                       frtm_stream_t stream);
 
+/* The DAVIS measures J and F (lib/davis.py: db_eval_iou, seg2bmap, db_eval_boundary) as exact integer counts (csrc/jf_eval.hip).
+ * pred / truth: DEVICE label maps [T][H][W], label_bytes = 1 (uint8) or 4 (int32); ids: HOST array of K object ids; r: radius of the
+ * matching disk {dy^2 + dx^2 <= r^2} in pixels, 1 ... 64.  counts: DEVICE int32 [T][K][6] = inter, union (of pred == id and
+ * truth == id), n_fg, n_gt (boundary pixels of either), fg_match, gt_match (boundary pixels with a boundary pixel of the other map
+ * inside the disk; zero outside the image).  ws: frtm_jf_workspace_bytes(T, H, W, K) bytes of device scratch (the boundary maps as
+ * bit planes).  H * W < 2^31 and T * K * 2 <= 65535 per call (the caller splits longer sequences over frames). */
+size_t frtm_jf_workspace_bytes(int T, int H, int W, int K);
+int frtm_jf_counts(const void* pred, const void* truth, int label_bytes, int T, int H, int W, const int* ids, int K, int r, int* counts,
+                   void* ws, size_t ws_bytes, frtm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
