@@ -22,27 +22,22 @@
 //   them in the same fixed order: identical scalars everywhere)                                                   | barriers C and D
 //   The new direction p' = z + beta p is linear, so the owners publish the composed rows of z BEFORE barrier D, together with the partial
 //   dots, and every workgroup forms F' = F_z + beta F locally afterwards: no fifth barrier.
-// 4 grid barriers (3 on the last iteration) per operator application, XCD-hierarchical as in cg_persistent.hip; same exchange protocol
-// (sc1 payloads, every storing wave drains, sc1 reads; polled words zeroed by memset nodes per launch; bounded spins).  A launch that
-// times out writes NOTHING back (commit XOR abort: workgroup 0 claims the launch's abort word behind a final barrier, see grid_sync) and
-// bumps the sticky abort counter; the host then falls back to the chain form (model/optimizer.py).
+// 4 grid barriers (3 on the last iteration) per operator application.  The barrier (XCD-hierarchical), the exchange protocol, the abort word
+// and the phases over the resident rows are those of the filter problem's kernel: resident_grid.h.  A launch that times out writes NOTHING
+// back (commit XOR abort: workgroup 0 claims the launch's abort word behind a final barrier) and bumps the sticky abort counter; the host
+// then falls back to the chain form (model/optimizer.py).
 // Results: the same algorithm as the chain form; dot products and slab sums have another (fixed) summation order and the new direction's
 // composed kernel is formed as F_z + beta F instead of from p' itself: rounding-level differences, gated like the filter problem's
 // persistent form (tests/test_round4_gpu.py).
-#include "frtm_common.h"
-#include "../../include/frtm_hip.h"
+#include "resident_grid.h"
 
 namespace {
 
-constexpr int NT = 512;            // threads per workgroup (8 waves: one workgroup per CU)
-constexpr int NWAVE = 8;
-constexpr int CPW = 12;            // channels per wave
+using namespace resident;          // NT, NWAVE, CPW, PW, FN (a group's direction filter / slab); the barrier, the sums and the phases
 constexpr int GCH = CPW * NWAVE;   // 96 channels per group
 constexpr int RMAX = 8;            // output rows per workgroup (8 + 4 halo rows x 12 channels = 144 feature registers per lane)
 constexpr int XR = RMAX + 4;       // feature rows held per lane
 constexpr int SR = RMAX + 2;       // score rows (stencil halo)
-constexpr int PW = 66;             // LDS row pitch of s / t (x = -1 .. 64)
-constexpr int FN = GCH * 9;        // 864: a group's direction filter / slab
 
 struct JParams {
   const float* X; const float* Z; const float* Bm; const float* cm; const float* sw;
@@ -56,99 +51,6 @@ struct JParams {
   float dff, lam1, lam2, invM1, invM2, step;
   long long spin_limit;
 };
-
-__device__ __forceinline__ void st_wt(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ float ld_l2(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// The launch's abort word has three states, every transition a compare-and-swap from 0:
-//   0 running   1 ABORTED (a workgroup gave up waiting; counted once in stats[2]; nobody writes anything back)
-//   2 COMMITTED (workgroup 0 claimed it behind the final barrier: every workgroup has arrived there and every workgroup writes its slices)
-// COMMIT XOR ABORT: a workgroup whose spin runs out in the very barrier the others have just passed either wins the word
-// (-> 1: nobody writes, workgroup 0's claim fails) or finds it committed (-> it has been waited for, the barrier is complete: it passes and
-// writes like everybody else).  A launch is never both counted as aborted and partially written.
-__device__ __forceinline__ bool give_up_or_committed(unsigned* abort_flag, unsigned* stats) {
-  unsigned expected = 0u;
-  const bool won = __hip_atomic_compare_exchange_strong(abort_flag, &expected, 1u, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (won && stats) __hip_atomic_fetch_add(stats + 2, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  return !won && expected == 2u;        // true: committed meanwhile (only possible in the final barrier, which is then complete)
-}
-
-__device__ __forceinline__ bool grid_sync(unsigned* counter, unsigned* abort_flag, unsigned* stats, unsigned target, long long limit, int* sh_flag) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // EVERY wave drains its write-through stores before the workgroup is counted
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const long long t0 = wall_clock64();
-    int ok = 1;
-    while (__hip_atomic_load(counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
-      __builtin_amdgcn_s_sleep(2);
-      if (__hip_atomic_load(abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 1u) { ok = 0; break; }
-      if (wall_clock64() - t0 > limit) { ok = give_up_or_committed(abort_flag, stats) ? 1 : 0; break; }
-    }
-    *sh_flag = ok;
-  }
-  __syncthreads();
-  return *sh_flag != 0;
-}
-
-// XCD-hierarchical barrier, layout and protocol of cg_persistent.hip (guide: "barrier-xcd")
-constexpr int HB_ARR = 0, HB_GEN = 128, HB_TOP = 256, HB_POP = 272, HB_WORDS = 288;
-__device__ __forceinline__ bool hier_sync(unsigned* hbar, unsigned* abort_flag, unsigned* stats, int xcc, unsigned n_x, unsigned n_active,
-                                          unsigned epoch, long long limit, int* sh_flag) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int ok = 1;
-    const long long t0 = wall_clock64();
-    const unsigned old = __hip_atomic_fetch_add(hbar + HB_ARR + 16 * xcc, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (old + 1u == epoch * n_x) {
-      __hip_atomic_fetch_add(hbar + HB_TOP, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      while (__hip_atomic_load(hbar + HB_TOP, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < epoch * n_active) {
-        __builtin_amdgcn_s_sleep(1);
-        if (__hip_atomic_load(abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 1u) { ok = 0; break; }
-        if (wall_clock64() - t0 > limit) { ok = give_up_or_committed(abort_flag, stats) ? 1 : 0; break; }
-      }
-      if (ok) __hip_atomic_store(hbar + HB_GEN + 16 * xcc, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    } else {
-      while (__hip_atomic_load(hbar + HB_GEN + 16 * xcc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < epoch) {
-        __builtin_amdgcn_s_sleep(1);
-        if (__hip_atomic_load(abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 1u) { ok = 0; break; }
-        if (wall_clock64() - t0 > limit) { ok = give_up_or_committed(abort_flag, stats) ? 1 : 0; break; }
-      }
-    }
-    *sh_flag = ok;
-  }
-  __syncthreads();
-  return *sh_flag != 0;
-}
-
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_add(float v) {
-  const int moved = __builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROW_MASK, 0xf, true);
-  return v + __int_as_float(moved);
-}
-__device__ __forceinline__ float wave_sum_to63(float v) {
-  v = dpp_add<0x111, 0xf>(v);
-  v = dpp_add<0x112, 0xf>(v);
-  v = dpp_add<0x114, 0xf>(v);
-  v = dpp_add<0x118, 0xf>(v);
-  v = dpp_add<0x142, 0xa>(v);
-  v = dpp_add<0x143, 0xc>(v);
-  return v;
-}
-// deterministic block sums of two values over NT threads (fixed butterfly + fixed wave order); all threads receive the totals
-__device__ __forceinline__ void bsum2(float& a, float& b, float* red) {
-  a = wave_sum_to63(a);
-  b = wave_sum_to63(b);
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 63) { red[wid] = a; red[16 + wid] = b; }
-  __syncthreads();
-  float ta = 0.f, tb = 0.f;
-#pragma unroll
-  for (int i = 0; i < NWAVE; ++i) { ta += red[i]; tb += red[16 + i]; }
-  a = ta; b = tb;
-}
 
 // LDS carve-up (floats) behind the six owned vector slices (6 * own_stride floats, own_stride from the host)
 constexpr int L_W2 = 0;                               // [96][9] filter.weight of this launch's linearisation point
@@ -186,7 +88,7 @@ __global__ __launch_bounds__(NT) void k_joint_run_persistent(const JParams P) {
   const int n_s = k / P.parts, part = k - n_s * P.parts;
   const int r0 = part * P.R;
   const int R = min(P.R, P.h - r0);
-  const int c = P.c, h = P.h, w = P.w, hw = h * w, Cin = P.Cin;
+  const int c = P.c, h = P.h, w = P.w, Cin = P.Cin;
   const bool zgrp = g == P.NGr;                       // the projected-feature group
   const int gbase = zgrp ? 0 : g * GCH;               // first channel of my group (in X or in Z)
   const int gcnt = zgrp ? c : min(GCH, Cin - gbase);  // channels of my group
@@ -197,38 +99,13 @@ __global__ __launch_bounds__(NT) void k_joint_run_persistent(const JParams P) {
   const int own = ocnt * per;
   const int vbase = zgrp ? n1 + o0 * 9 : (gbase + o0) * c;       // first global vector index of the owned slice (contiguous)
   const float lam = zgrp ? P.lam2 : P.lam1, invM = zgrp ? P.invM2 : P.invM1;
-  unsigned* counter = P.bar;
-  unsigned* abort_flag = P.bar + 2;
-  unsigned epoch = 0;
+  GridBarrier gb(P.bar, P.hbar, P.stats, P.spin_limit, sh_flag_p);
 
   // ---- resident data ----
   float xr[CPW][XR];
-  {
-    const float* src = zgrp ? P.Z + (size_t)n_s * c * hw : P.X + ((size_t)n_s * Cin + gbase) * hw;
-#pragma unroll
-    for (int kk = 0; kk < CPW; ++kk) {
-      const int ch = wid * CPW + kk;
-      const float* Xc = src + (size_t)min(ch, gcnt - 1) * hw;
-#pragma unroll
-      for (int i = 0; i < XR; ++i) {
-        const int yy = r0 - 2 + i;
-        const bool ok = ch < gcnt && lane < w && (unsigned)yy < (unsigned)h && i < P.R + 4;
-        xr[kk][i] = ok ? Xc[yy * w + lane] : 0.f;
-      }
-    }
-  }
-  for (int i = tid; i < 9 * RMAX * 64; i += NT) {
-    const int d = i / (RMAX * 64), rr = (i / 64) % RMAX, x = i & 63;
-    (&Bl[0][0][0])[i] = (rr < R && x < w) ? P.Bm[((size_t)n_s * 9 + d) * hw + (r0 + rr) * w + x] : 0.f;
-  }
-  for (int i = tid; i < RMAX * 64; i += NT) {
-    const int rr = i / 64, x = i & 63;
-    (&cl[0][0])[i] = (rr < R && x < w) ? P.cm[(size_t)n_s * hw + (r0 + rr) * w + x] : 0.f;
-  }
-  for (int i = tid; i < SR * PW; i += NT) (&sl[0][0])[i] = 0.f;
-  for (int i = tid; i < RMAX * PW; i += NT) (&tl[0][0])[i] = 0.f;
+  load_rows<RMAX>(xr, zgrp ? P.Z : P.X, zgrp ? (size_t)n_s * c : (size_t)n_s * Cin + gbase, gcnt, h, w, r0, P.R, lane, wid);
+  load_maps<RMAX>(Bl, cl, sl, tl, P.Bm, P.cm, n_s, h, w, r0, R);
   for (int i = tid; i < FN; i += NT) { w2l[i] = i < c * 9 ? P.w2[i] : 0.f; vF[i] = 0.f; vFz[i] = 0.f; gx[i] = 0.f; }
-  if (tid == 0) sh_flag_p[0] = 1;
   for (int i = tid; i < OS; i += NT) {
     const bool on = i < own;
     // variables of the owned slice: raw groups rows of w1T (Cin x c), the Z group rows of w2 (c x 9)
@@ -238,34 +115,7 @@ __global__ __launch_bounds__(NT) void k_joint_run_persistent(const JParams P) {
     vb[i] = vr[i] = vq[i] = vx[i] = 0.f;
   }
   const float swn = P.sw[n_s];
-  // ---- XCD registration (as cg_persistent.hip), then ONE flat barrier ----
-  const bool hier = P.hbar != nullptr;
-  int xcc = 0; unsigned n_x = 1, n_active = 1, hepoch = 0;
-  if (hier) {
-    if (tid == 0) {
-      const int xx = (int)(__builtin_amdgcn_s_getreg((3 << 11) | 20) & 7u);          // HW_REG_XCC_ID
-      sh_flag_p[1] = xx;
-      __hip_atomic_fetch_add(P.hbar + HB_POP + xx, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
-    if (!grid_sync(counter, abort_flag, P.stats, (++epoch) * (unsigned)G, P.spin_limit, sh_flag_p)) return;
-    if (tid == 0) {
-      unsigned act = 0, mine = 0;
-      for (int xx = 0; xx < 8; ++xx) {
-        const unsigned c_ = __hip_atomic_load(P.hbar + HB_POP + xx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        act += c_ > 0u ? 1u : 0u;
-        if (xx == sh_flag_p[1]) mine = c_;
-      }
-      sh_flag_p[2] = (int)mine; sh_flag_p[3] = (int)act;
-    }
-    __syncthreads();
-    xcc = sh_flag_p[1]; n_x = (unsigned)sh_flag_p[2]; n_active = (unsigned)sh_flag_p[3];
-  }
-  auto gsync = [&]() -> bool {
-    if (hier) return hier_sync(P.hbar, abort_flag, P.stats, xcc, n_x, n_active, ++hepoch, P.spin_limit, sh_flag_p);
-    return grid_sync(counter, abort_flag, P.stats, (++epoch) * (unsigned)G, P.spin_limit, sh_flag_p);
-  };
-  __syncthreads();
+  if (!gb.join()) return;                             // XCD registration behind ONE flat barrier; ends in a workgroup barrier (LDS above is set up)
 
   // ---- composed rows of an owned vector slice -> Fbuf[slot][g][(o0 + chl) * 9 + tap]  (raw groups: v . w2; Z group: v itself) ----
   auto publish_compose = [&](const float* v, int slot) {
@@ -306,39 +156,11 @@ __global__ __launch_bounds__(NT) void k_joint_run_persistent(const JParams P) {
     // 1. partial scores of the own channels: three column partials per score row
     float* sp = P.spart + ((size_t)k * NG + g) * (SR * 64);
     if (scores_on) {
-      float S0[SR], S1[SR], S2[SR];
-#pragma unroll
-      for (int jj = 0; jj < SR; ++jj) { S0[jj] = 0.f; S1[jj] = 0.f; S2[jj] = 0.f; }
-#pragma unroll
-      for (int kk = 0; kk < CPW; ++kk) {
-        const float* f = vF + (wid * CPW + kk) * 9;          // LDS broadcast reads (zero beyond the group's channels)
-#pragma unroll
-        for (int dy = 0; dy < 3; ++dy) {
-          const float f0 = f[dy * 3 + 0], f1 = f[dy * 3 + 1], f2_ = f[dy * 3 + 2];
-#pragma unroll
-          for (int jj = 0; jj < SR; ++jj) {
-            const float xv = xr[kk][jj + dy];
-            S0[jj] += f0 * xv; S1[jj] += f1 * xv; S2[jj] += f2_ * xv;
-          }
-        }
-      }
-#pragma unroll
-      for (int jj = 0; jj < SR; ++jj) {
-        const float l = __shfl_up(S0[jj], 1, 64), r = __shfl_down(S2[jj], 1, 64);
-        red[wid][jj][lane] = (lane > 0 ? l : 0.f) + S1[jj] + (lane < 63 ? r : 0.f);
-      }
-      __syncthreads();
-      for (int i = tid; i < SR * 64; i += NT) {
-        const int jj = i >> 6, x = i & 63;
-        float s = 0.f;
-#pragma unroll
-        for (int q = 0; q < NWAVE; q += 4) s += (red[q][jj][x] + red[q + 1][jj][x]) + (red[q + 2][jj][x] + red[q + 3][jj][x]);
-        st_wt(sp + i, s);
-      }
+      partial_scores<RMAX>(xr, vF, red, [&](int i, float s) { st_wt(sp + i, s); });          // (vF: zero beyond the group's channels)
     } else {
       for (int i = tid; i < SR * 64; i += NT) st_wt(sp + i, 0.f);
     }
-    if (!gsync()) return false;                                                       // ---- barrier A
+    if (!gb.sync()) return false;                                                       // ---- barrier A
     // 2. the full score rows of (n, part): sum of the NG partial maps, fixed order; then the stencil
     for (int i = tid; i < SR * 64; i += NT) {
       const int jj = i >> 6, x = i & 63;
@@ -349,49 +171,10 @@ __global__ __launch_bounds__(NT) void k_joint_run_persistent(const JParams P) {
       sl[jj][x + 1] = (x < w && (unsigned)yy < (unsigned)h && jj < R + 2) ? s : 0.f;
     }
     __syncthreads();
-    for (int rr = wid; rr < RMAX; rr += NWAVE) {
-      float acc = 0.f;
-      if (rr < R && lane < w) {
-#pragma unroll
-        for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-          for (int dx = 0; dx < 3; ++dx) acc += Bl[dy * 3 + dx][rr][lane] * sl[rr + dy][lane + dx];
-        if (with_c) acc -= cl[rr][lane];
-        acc *= swn;
-      }
-      tl[rr][lane + 1] = acc;
-    }
-    __syncthreads();
+    stencil<RMAX>(Bl, cl, sl, tl, R, w, with_c, swn);
     // 3. weight gradient of the own channels from the resident rows
-    float tv[RMAX][3];
-#pragma unroll
-    for (int rr = 0; rr < RMAX; ++rr)
-#pragma unroll
-      for (int dx = 0; dx < 3; ++dx) tv[rr][dx] = tl[rr][lane + 2 - dx];
-#pragma unroll
-    for (int kk = 0; kk < CPW; ++kk) {
-      float a[9];
-#pragma unroll
-      for (int e = 0; e < 9; ++e) a[e] = 0.f;
-#pragma unroll
-      for (int rr = 0; rr < RMAX; ++rr)
-#pragma unroll
-        for (int dy = 0; dy < 3; ++dy) {
-          const float xv = xr[kk][rr + dy + 1];
-#pragma unroll
-          for (int dx = 0; dx < 3; ++dx) a[dy * 3 + dx] += tv[rr][dx] * xv;
-        }
-      float* dst = gl + (wid * CPW + kk) * 9;
-#pragma unroll
-      for (int e = 0; e < 9; ++e) {
-        const float tot = wave_sum_to63(a[e]);
-        if (lane == 63) dst[e] = tot;
-      }
-    }
-    __syncthreads();
-    float* slab = P.slabs + ((size_t)g * KK + k) * FN;
-    for (int i = tid; i < FN; i += NT) st_wt(slab + i, gl[i]);
-    if (!gsync()) return false;                                                       // ---- barrier B
+    weight_gradient<RMAX>(xr, tl, gl, P.slabs + ((size_t)g * KK + k) * FN);
+    if (!gb.sync()) return false;                                                       // ---- barrier B
     // 4. owners: sum of the KK slabs of the owned channels (one wave per element, fixed order), then the expansion through w2
     for (int e0 = wid; e0 < ocnt * 9; e0 += NWAVE) {
       const int e = o0 * 9 + e0;
@@ -440,7 +223,7 @@ __global__ __launch_bounds__(NT) void k_joint_run_persistent(const JParams P) {
     bsum2(d0, d1, sred);
     publish_dots(d0, d1, 0);
     publish_compose(vx, 0);                            // composed rows of z (slot 0)
-    if (!gsync()) return;                                                              // ---- barrier C'
+    if (!gb.sync()) return;                                                              // ---- barrier C'
     sum_dots(d0, d1, 0);
     float beta = 0.f;
     if (P.has_p) {
@@ -469,7 +252,7 @@ __global__ __launch_bounds__(NT) void k_joint_run_persistent(const JParams P) {
     for (int i = tid; i < OS; i += NT) { pq += vp[i] * vq[i]; pr += vp[i] * vr[i]; }
     bsum2(pq, pr, sred);
     publish_dots(pq, pr, 1);
-    if (!gsync()) return;                                                              // ---- barrier C
+    if (!gb.sync()) return;                                                              // ---- barrier C
     sum_dots(pq, pr, 1);
     alpha = P.std_alpha ? rho_cur / pq : pr / pq;
     float rn_ = 0.f, r2_ = 0.f;
@@ -490,7 +273,7 @@ __global__ __launch_bounds__(NT) void k_joint_run_persistent(const JParams P) {
       bsum2(rn_, r2_, sred);
       publish_dots(rn_, r2_, 0);
       publish_compose(vq, 0);
-      if (!gsync()) return;                                                            // ---- barrier D
+      if (!gb.sync()) return;                                                            // ---- barrier D
       sum_dots(rn_, r2_, 0);
       const float vv = P.fr ? rn_ / rho_cur : (rn_ - r2_) / rho_cur;
       beta_last = (vv < 0.f) ? 0.f : vv;
@@ -503,21 +286,16 @@ __global__ __launch_bounds__(NT) void k_joint_run_persistent(const JParams P) {
     __syncthreads();
   }
   // ---- write back: every workgroup its owned slices, behind a final barrier, and only if the launch COMMITS (protocol at grid_sync) ----
-  if (!gsync()) return;
+  if (!gb.sync()) return;
   if (tid == 0) {
     unsigned st;
-    if (bid == 0) {
-      // the claim: 0 -> 2 (committed; stats[3] counts committed launches), or somebody gave up first (1)
-      unsigned expected = 0u;
-      const bool won = __hip_atomic_compare_exchange_strong(abort_flag, &expected, 2u, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      st = won ? 2u : expected;
-      if (won && P.stats) __hip_atomic_fetch_add(P.stats + 3, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    } else {
+    if (bid == 0) st = claim_commit(gb.abort_flag(), P.stats);
+    else {
       // wait for workgroup 0's decision (it is resident and a few instructions away) -- bounded like every other wait
       const long long t0 = wall_clock64();
-      while ((st = __hip_atomic_load(abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == 0u) {
+      while ((st = __hip_atomic_load(gb.abort_flag(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == 0u) {
         __builtin_amdgcn_s_sleep(1);
-        if (wall_clock64() - t0 > P.spin_limit) { st = give_up_or_committed(abort_flag, P.stats) ? 2u : 1u; break; }
+        if (wall_clock64() - t0 > P.spin_limit) { st = give_up_or_committed(gb.abort_flag(), P.stats) ? 2u : 1u; break; }
       }
     }
     sh_flag_p[0] = st == 2u ? 1 : 0;
@@ -548,18 +326,11 @@ __global__ __launch_bounds__(NT) void k_joint_run_persistent(const JParams P) {
 
 extern "C" {
 
-static int joint_budget() {
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return 240; }
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) { (void)hipGetLastError(); cus = 256; }
-  return cus - cus / 16;
-}
-
 // Workgroups of the resident form of the joint problem (0: the problem does not fit).  out4 = {parts, rows per part, owned channels per
 // workgroup, floats of one owned vector slice in LDS}.
 int frtm_joint_persistent_plan(int N, int Cin, int c, int h, int w, int* out4) {
   if (N < 1 || Cin < 1 || c < 1 || c > GCH || w < 1 || w > 64 || h < 1) return 0;
-  const int budget = joint_budget();
+  const int budget = resident_budget();
   const int NG = ceil_div(Cin, GCH) + 1;
   const int min_parts = ceil_div(h, RMAX);
   if ((long)NG * N * min_parts > budget) return 0;
@@ -604,15 +375,14 @@ int frtm_joint_run_persistent(const float* X, const float* Z, const float* Bm, c
   P.N = N; P.Cin = Cin; P.c = c; P.h = h; P.w = w; P.R = o[1]; P.parts = o[0]; P.NGr = NG - 1; P.cpo = o[2]; P.own_stride = o[3];
   P.iters = iters; P.has_p = has_p; P.apply_dff = apply_dff; P.fr = fletcher_reeves; P.std_alpha = standard_alpha;
   P.dff = dff; P.lam1 = lam1; P.lam2 = lam2; P.invM1 = invM1; P.invM2 = invM2; P.step = step;
-  P.spin_limit = debug_abort ? 0LL : 400000LL;
+  P.spin_limit = resident_spin_limit(debug_abort);
   const size_t lds = (size_t)(L_FIXED + 7 * o[3]) * 4;
   static size_t attr_lds = 0;
   if (lds > attr_lds) {
     FRTM_HIP(hipFuncSetAttribute((const void*)k_joint_run_persistent, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     attr_lds = lds;
   }
-  FRTM_HIP(hipMemsetAsync(bar, 0, 3 * sizeof(unsigned), (hipStream_t)stream));
-  if (hbar) FRTM_HIP(hipMemsetAsync(hbar, 0, HB_WORDS * sizeof(unsigned), (hipStream_t)stream));
+  if (int e = resident_reset_words(bar, hbar, (hipStream_t)stream)) return e;
   k_joint_run_persistent<<<G, NT, lds, (hipStream_t)stream>>>(P);
   FRTM_LAUNCH_CHECK();
   return FRTM_OK;

@@ -19,6 +19,8 @@ import torch
 from .. import _hip as H
 from ..lib.tensorlist import TensorList
 
+HBAR_WORDS = 288        # FRTM_HBAR_WORDS of include/frtm_hip.h: int32 words of the resident solvers' XCD-hierarchical barrier state
+
 
 class MinimizationProblem:
     """Protocol of a least-squares problem handled by GaussNewtonCG.
@@ -72,8 +74,12 @@ class GaussNewtonCG:
         self._n = None
         self._has_p = False
         self._buf = None
-        self._pbuf = None
+        self._pbuf = None                # exchange buffers of the filter problem's resident form (_filter_exchange)
+        self._jbuf = None                # exchange buffers of the joint problem's resident form (_joint_exchange)
+        self._guard = None               # (device count, minimum) while a guarded run() is in progress
+        self._last_of_run = True         # the Gauss-Newton iteration being enqueued is the last of its run()
         self._persistent_launched = False
+        self._joint_launched = False     # this object's fit has launched in the resident form of the joint problem
         self._gstats = None              # device int32[4]: guarded runs completed / skipped by the device-side early-out, persistent launches
                                          # aborted / persistent launches COMMITTED (wrote x and the solver state back)
         self._launched = []              # num_cg_iter of every persistent launch since the last poll (oldest first)
@@ -101,12 +107,26 @@ class GaussNewtonCG:
         self._stats()
         pr = self.problem
         if getattr(pr, 'joint', False) and hasattr(pr, 'persistent_joint_args'):
-            need = int(H.lib().frtm_joint_persistent_scratch(int(pr.mem.capacity), int(pr.Cin), int(pr.c), int(pr.h), int(pr.w)))
-            if need > 0 and (getattr(self, '_jbuf', None) is None or self._jbuf[0].numel() < need):
-                self._jbuf = (torch.empty(need, device=dev), torch.zeros(4, dtype=torch.int32, device=dev), torch.zeros(288, dtype=torch.int32, device=dev))
-        elif hasattr(pr, 'persistent_args') and self._pbuf is None:      # the filter problem's resident form (its exchange slabs)
+            self._joint_exchange(int(pr.mem.capacity), int(pr.Cin), int(pr.c), int(pr.h), int(pr.w))
+        elif hasattr(pr, 'persistent_args'):
+            self._filter_exchange()
+
+    def _filter_exchange(self):
+        """(slabs, qbuf, bar, hbar) of the filter problem's resident form, allocated once."""
+        if self._pbuf is None:
+            dev = self._buf.device
             self._pbuf = (torch.empty(256 * 864, device=dev), torch.zeros(864 + 256, device=dev), torch.zeros(4, dtype=torch.int32, device=dev),
-                          torch.zeros(288, dtype=torch.int32, device=dev))
+                          torch.zeros(HBAR_WORDS, dtype=torch.int32, device=dev))
+        return self._pbuf
+
+    def _joint_exchange(self, N, Cin, c, h, w):
+        """(scratch, bar, hbar) of the joint problem's resident form for N samples; grows, never shrinks.  A problem that does not fit the
+        resident form (scratch size 0) allocates nothing."""
+        need = int(H.lib().frtm_joint_persistent_scratch(N, Cin, c, h, w))
+        if need > 0 and (self._jbuf is None or self._jbuf[0].numel() < need):
+            dev = self._buf.device
+            self._jbuf = (torch.empty(need, device=dev), torch.zeros(4, dtype=torch.int32, device=dev), torch.zeros(HBAR_WORDS, dtype=torch.int32, device=dev))
+        return self._jbuf
 
     @property
     def b(self):
@@ -246,11 +266,7 @@ class GaussNewtonCG:
         launch.  Host-side bookkeeping as in run_CG."""
         pr = self.problem
         pr.prepare_linearization()
-        if getattr(self, '_jbuf', None) is None or self._jbuf[0].numel() < int(H.lib().frtm_joint_persistent_scratch(a['N'], a['Cin'], a['c'], a['h'], a['w'])):
-            dev = self._buf.device
-            self._jbuf = (torch.empty(int(H.lib().frtm_joint_persistent_scratch(a['N'], a['Cin'], a['c'], a['h'], a['w'])), device=dev),
-                          torch.zeros(4, dtype=torch.int32, device=dev), torch.zeros(288, dtype=torch.int32, device=dev))
-        scratch, bar, hbar = self._jbuf
+        scratch, bar, hbar = self._joint_exchange(a['N'], a['Cin'], a['c'], a['h'], a['w'])
         stats = self._stats()
         dff = float(self.direction_forget_factor)
         if dff == 0:
@@ -269,7 +285,7 @@ class GaussNewtonCG:
     def joint_aborts(self):
         """Aborted resident launches of the joint problem so far (stats[2]).  SYNCHRONISES; an aborted launch wrote nothing, i.e. that
         Gauss-Newton iteration is MISSING from the fit: the caller re-runs the fit in the chain form (Discriminator.init / Tracker)."""
-        if not getattr(self, '_joint_launched', False) or self._gstats is None:
+        if not self._joint_launched or self._gstats is None:
             return 0
         return int(self._gstats[2].item())
 
@@ -284,13 +300,9 @@ class GaussNewtonCG:
 
     def _run_persistent(self, num_cg_iter, a):
         """linearize + run_CG + apply_step of run_GN_iter in ONE launch; host-side bookkeeping as in run_CG."""
-        if self._pbuf is None:
-            dev = self._buf.device
-            self._pbuf = (torch.empty(256 * 864, device=dev), torch.zeros(864 + 256, device=dev), torch.zeros(4, dtype=torch.int32, device=dev),
-                          torch.zeros(288, dtype=torch.int32, device=dev))
-        slabs, qbuf, bar, hbar = self._pbuf
+        slabs, qbuf, bar, hbar = self._filter_exchange()
         stats = self._stats()
-        guard, guard_min = self._guard if getattr(self, '_guard', None) is not None else (None, 0)
+        guard, guard_min = self._guard if self._guard is not None else (None, 0)
         dff = float(self.direction_forget_factor)
         if dff == 0:
             self.reset_state()
@@ -300,7 +312,7 @@ class GaussNewtonCG:
                int(num_cg_iter), int(self._has_p), int(self._has_p and dff != 0), int(self.fletcher_reeves), int(self.standard_alpha),
                dff if dff != 0 else 1.0, float(a['lam2']), 1.0 / m1, float(self.step_alpha),
                None if guard is None else guard.data_ptr(), guard_min, H.ptr(stats),
-               int(guard is not None and getattr(self, '_last_of_run', True)), int(bool(self.debug_abort)),
+               int(guard is not None and self._last_of_run), int(bool(self.debug_abort)),
                H.ptr(hbar) if self.hierarchical_barrier else None)
         self._has_p = True
         self._persistent_launched = True

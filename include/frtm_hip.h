@@ -192,6 +192,7 @@ int frtm_joint_expand(const float* G, int nslab, const float* w2, int Cin, int c
  * frtm_cg_persistent_plan returns the number of workgroups (0 = shape not supported: w > 64, c > 96, or N*ceil(h/10) above the
  * resident budget = 15/16 of the current device's CUs, 240 on an MI355X); all of them must be resident at once: never run two of these
  * launches concurrently on one GPU. */
+#define FRTM_HBAR_WORDS 288   /* unsigned words of `hbar`, the XCD-hierarchical barrier's state, in both resident solvers (layout: csrc/resident_grid.h) */
 int frtm_cg_persistent_plan(int N, int c, int h, int w, int* parts_out, int* rows_out);
 int frtm_cg_run_persistent(const float* X, const float* Bm, const float* cm, const float* sw, int N, int c, int h, int w,
                            float* w2, float* vec, float* state, float* slabs, float* qbuf, unsigned* bar,
@@ -202,7 +203,7 @@ int frtm_cg_run_persistent(const float* X, const float* Bm, const float* cm, con
  * touching anything.  stats (device unsigned[4], optional): with count_run != 0, [0] += 1 per completed launch, [1] += 1 per guarded
  * early-out; [2] += 1 per ABORTED launch (always).  debug_abort != 0 forces the time-out (tests of the caller's fallback).  The host
  * never waits for the pixel count, so a tracking loop enqueues whole sequences without a device->host read.
- * hbar (device unsigned[288], optional): state of the XCD-hierarchical grid barrier (zeroed by the launch); NULL: flat barrier. */
+ * hbar (device unsigned[FRTM_HBAR_WORDS], optional): state of the XCD-hierarchical grid barrier (zeroed by the launch); NULL: flat barrier. */
 int frtm_cg_run_persistent_guarded(const float* X, const float* Bm, const float* cm, const float* sw, int N, int c, int h, int w,
                                    float* w2, float* vec, float* state, float* slabs, float* qbuf, unsigned* bar,
                                    int iters, int has_p, int apply_dff, int fletcher_reeves, int standard_alpha, float dff,
@@ -230,7 +231,7 @@ int frtm_cg_step_small(const float* slabs, int nslab, int stride, float lam2, fl
  * workgroup, floats per owned vector slice}.  scratch: floats of exchange scratch a launch needs.
  * w1T (Cin, c) = project.weight transposed at the linearisation point (input); w1 (c, Cin) and w2 (c, 9) are UPDATED in place; vec / state
  * as in frtm_cg_*: vec = [b, r, r_prev, p, q, delta] x (Cin c + 9 c) with the projection part stored transposed, state[0] = rho ...
- * bar: >= 3 zero-initialised words (zeroed again by every launch); hbar: 288 words or NULL (flat barrier); stats (may be NULL):
+ * bar: >= 3 zero-initialised words (zeroed again by every launch); hbar: FRTM_HBAR_WORDS words or NULL (flat barrier); stats (may be NULL):
  * [2] += 1 if the launch timed out (nothing is written back then), [3] += 1 if it committed.
  * ------------------------------------------------------------------------------------------ */
 int frtm_joint_persistent_plan(int N, int Cin, int c, int h, int w, int* out4);

@@ -109,3 +109,55 @@ def test_gemm_kernel_k_loop_carries_no_address_arithmetic(igemm_isa, inst, mfmas
     tail_form = [l for l in valu if re.search(r'v_cndmask|v_cmp|v_bfrev|v_subrev', l)]
     straight = [l for l in valu if l not in tail_form]
     assert len(straight) <= 2 * 6, straight
+
+
+# ---- the resident solvers (csrc/cg_persistent.hip, csrc/joint_persistent.hip on csrc/resident_grid.h) ----
+BUILD_FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wall', '-Wno-unused-function']     # frtm-vos_amd/build.py
+
+
+@pytest.fixture(scope='module')
+def resident_isa():
+    if not os.path.exists(HIPCC):
+        pytest.skip('no hipcc')
+    isa = {}
+    with tempfile.TemporaryDirectory() as d:
+        for stem in ('cg_persistent', 'joint_persistent'):
+            out = os.path.join(d, stem + '.s')
+            subprocess.run([HIPCC] + BUILD_FLAGS + ['-S', '--cuda-device-only', '-o', out, os.path.join(ROOT, 'frtm-vos_amd', 'csrc', stem + '.hip')],
+                           check=True, capture_output=True, cwd=d)
+            isa[stem] = open(out).read()
+    return isa
+
+
+def _kernel_metadata(isa, kernel):
+    """The integer fields of one kernel's entry in the amdhsa.kernels metadata."""
+    entries = [e for e in re.split(r'\n  - ', isa[isa.index('amdhsa.kernels:'):]) if re.search(r'\.name:\s+\S*%s\S*\n' % kernel, e)]
+    assert len(entries) == 1, kernel
+    return {k: int(v) for k, v in re.findall(r'\.(\w+):\s+(\d+)\s*$', entries[0], flags=re.M)}
+
+
+# sgpr spills / sc1 stores / sc1 loads of the two files as compiled before the kernels moved onto resident_grid.h.  If a later compiler merges
+# or splits accesses, re-derive the counts from the listing (and check every payload access by hand); do not drop them.
+@pytest.mark.parametrize('stem,kernel,sgpr_spills,sc1_stores,sc1_loads', [('cg_persistent', 'k_cg_run_persistent', 0, 8, 38),
+                                                                           ('joint_persistent', 'k_joint_run_persistent', 48, 22, 72)])
+def test_resident_solvers_fit_a_cu_and_keep_their_write_through_accesses(resident_isa, stem, kernel, sgpr_spills, sc1_stores, sc1_loads):
+    """Both resident solvers run 512 threads per workgroup = two waves per SIMD, i.e. at most 256 VGPRs per lane: one register more and the workgroup no
+    longer fits a CU, which for a grid that must be co-resident means that EVERY launch times out (k_cg_run_persistent uses 254).  Spilled vector
+    registers or scratch would put memory traffic into the phases between the barriers.  And every exchanged payload must stay a write-through
+    (sc1) store / an L1-bypassing (sc1) load: one that silently became a plain access is stale data that no functional test on an idle GPU sees."""
+    isa = resident_isa[stem]
+    md = _kernel_metadata(isa, kernel)
+    assert md['vgpr_spill_count'] == 0
+    assert md['private_segment_fixed_size'] == 0
+    assert md['vgpr_count'] <= 256
+    assert md['sgpr_spill_count'] <= sgpr_spills
+    assert len(re.findall(r'global_store_dword.* sc1', isa)) >= sc1_stores
+    assert len(re.findall(r'global_load_dword.* sc1', isa)) >= sc1_loads
+
+
+def test_barrier_state_size_is_one_number():
+    """The host allocates the XCD-hierarchical barrier's state (model/optimizer.py), the kernels lay it out (csrc/resident_grid.h asserts its
+    HB_WORDS against the same define at compile time)."""
+    from frtm_vos_amd.model import optimizer
+    header = open(os.path.join(ROOT, 'include', 'frtm_hip.h')).read()
+    assert optimizer.HBAR_WORDS == int(re.search(r'#define FRTM_HBAR_WORDS (\d+)', header).group(1))
