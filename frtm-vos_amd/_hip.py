@@ -134,6 +134,11 @@ SIGNATURES = {
     'frtm_blur_gauss2d': (I, [P, I, I, I, I, F, F, F, P, P]),
     'frtm_jf_workspace_bytes': (ctypes.c_size_t, [I, I, I, I]),
     'frtm_jf_counts': (I, [P, P, I, I, I, I, ctypes.POINTER(I), I, I, P, P, ctypes.c_size_t, P]),
+    'frtm_bce_logits_workspace_bytes': (ctypes.c_size_t, [I, I, I]),
+    'frtm_bce_logits': (I, [P, P, I, I, I, I, P, P, P, P, P, ctypes.c_size_t, P]),
+    'frtm_scale_by': (I, [P, ctypes.c_size_t, P, P]),
+    'frtm_adam_chunk_elems': (I, []),
+    'frtm_adam_amsgrad': (I, [P, I, P, I, D, D, D, D, D, D, D, I, P]),
 }
 
 _lib = None

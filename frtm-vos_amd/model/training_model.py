@@ -12,9 +12,12 @@ the target model is fitted on the augmented first frame and its two weight tenso
                      meta) -> stats dict``, refiner-only checkpoints under the 'refiner.' prefix): per sample set, frame 0 goes to the bank,
                      every later frame contributes one BCE backward pass through the refiner: its PyTorch definition
                      (``SegNetwork.forward_torch``, the default) or, with ``refiner_backend='hip'``, its HIP training pass
-                     (``SegNetwork.forward_train``: forward and backward on the project's kernels).
+                     (``SegNetwork.forward_train``: forward and backward on the project's kernels).  ``loss_backend='hip'`` takes the
+                     loss, its gradient and the IoU counts from one HIP pass over the logits (model/train_loss.py) and keeps the running
+                     loss / accuracy on the device: one read-back per call instead of two per frame.
 
-The training DRIVER (optimiser, schedule, data loaders, logging: train.py, lib/training.py) is out of scope.
+The training driver lives in lib/training.py (Trainer), lib/training_datasets.py (sample sets), lib/fused_adam.py (the optimiser step on
+HIP) and train.py (command line).
 """
 import json
 from pathlib import Path
@@ -24,6 +27,7 @@ import torch.nn as nn
 
 from ..lib.utils import interpolate
 from .discriminator import Discriminator
+from .train_loss import bce_logits_stats, iou_from_counts
 
 
 class SampleSpec:
@@ -137,13 +141,18 @@ def mask_iou(pred, gt):
 class TrainerModel(nn.Module):
 
     def __init__(self, augmenter, feature_extractor, disc_params, seg_network, batch_size=0, tmodel_cache=None, device=None,
-                 refiner_backend='torch'):
+                 refiner_backend='torch', loss_backend='torch'):
         """refiner_backend: 'torch' runs the refiner's training pass through its PyTorch definition (forward_torch), 'hip' through
-        SegNetwork.forward_train (HIP kernels forward and backward)."""
+        SegNetwork.forward_train (HIP kernels forward and backward).
+        loss_backend: 'torch' = sigmoid + nn.BCELoss + mask_iou on framework kernels, read back after every frame; 'hip' = the
+        loss tail of model/train_loss.py on the logits, statistics accumulated on the device and read back once per call."""
         if refiner_backend not in ('torch', 'hip'):
             raise ValueError("refiner_backend must be 'torch' or 'hip', not %r" % (refiner_backend,))
+        if loss_backend not in ('torch', 'hip'):
+            raise ValueError("loss_backend must be 'torch' or 'hip', not %r" % (loss_backend,))
         super().__init__()
         self.refiner_backend = refiner_backend
+        self.loss_backend = loss_backend
         self.augmenter = augmenter
         self.feature_extractor = feature_extractor
         self.refiner = seg_network
@@ -171,7 +180,8 @@ class TrainerModel(nn.Module):
         self.refiner.load_state_dict({k[len('refiner.'):]: v for k, v in state_dict.items()})
 
     def _predict(self, image):
-        """sigmoid(refiner(score, taps)) for a batch of frames: trunk and target models frozen on the HIP path, the refiner with autograd."""
+        """sigmoid(refiner(score, taps)) for a batch of frames (the logits themselves with loss_backend='hip'): trunk and target models
+        frozen on the HIP path, the refiner with autograd."""
         with torch.no_grad():
             taps = self.feature_extractor(image)
             scores = self.bank.scores(taps[self.bank.layer])
@@ -181,6 +191,8 @@ class TrainerModel(nn.Module):
                 logits = self.refiner.forward_train(scores, taps, image.shape)
             else:
                 logits = self.refiner.forward_torch(scores, taps, image.shape)
+            if self.loss_backend == 'hip':
+                return logits                                     # (already at the image size: both heads resize to image.shape)
             return torch.sigmoid(interpolate(logits, image.shape[-2:]))
 
     def forward(self, images, labels, meta):
@@ -189,6 +201,8 @@ class TrainerModel(nn.Module):
         specs = SampleSpec.from_encoded(meta)
         hits = self.bank.fit_or_load(images[0], labels[0], specs, self.tmodel_cache, self.augmenter.augment_first_frame,
                                      self.feature_extractor, self.device)
+        if self.loss_backend == 'hip':
+            return self._forward_hip_loss(images, labels, hits)
         loss_sum, acc_sum, n = 0.0, 0.0, 0
         for image, label in zip(images[1:], labels[1:]):
             pred = self._predict(image.to(self.device))
@@ -199,5 +213,24 @@ class TrainerModel(nn.Module):
             loss_sum += float(loss)
             acc_sum += float(self.compute_accuracy(pred.detach(), target).mean())
             n += 1
+        n = max(n, 1)
+        return {'stats/loss': loss_sum / n, 'stats/accuracy': acc_sum / n, 'stats/fcache_hits': hits}
+
+    def _forward_hip_loss(self, images, labels, hits):
+        sums = None                                               # (2,) on the device: sum of the frames' losses, of their mean IoUs
+        n = 0
+        for image, label in zip(images[1:], labels[1:]):
+            logits = self._predict(image.to(self.device))
+            target = label.to(self.device)
+            if target.dtype != torch.uint8:
+                target = target.float()
+            with torch.enable_grad():
+                loss, inter, union = bce_logits_stats(logits, target)
+            loss.backward()
+            with torch.no_grad():
+                frame = torch.stack([loss.detach(), iou_from_counts(inter, union).mean()])
+                sums = frame if sums is None else sums + frame
+            n += 1
+        loss_sum, acc_sum = sums.tolist() if sums is not None else (0.0, 0.0)       # the one device -> host read of the call
         n = max(n, 1)
         return {'stats/loss': loss_sum / n, 'stats/accuracy': acc_sum / n, 'stats/fcache_hits': hits}

@@ -292,3 +292,59 @@ def jf_counts(pred, truth, obj_ids, radius):
         H.call('frtm_jf_counts', H.ptr(pred[t0:t0 + n]), H.ptr(truth[t0:t0 + n]), pred.element_size(), n, Hh, Ww, ids_c, K, r,
                H.ptr(counts[t0:t0 + n]), H.ptr(ws), ws.numel())
     return counts
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# The ends of a training step (csrc/train_step.hip; model/train_loss.py, lib/fused_adam.py)
+# ----------------------------------------------------------------------------------------------------------------------
+def _aligned16(t):
+    return t if t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.contiguous_format)
+
+
+def bce_logits(logits, target, grad=True):
+    """The loss tail in one pass (frtm_bce_logits): logits (N,1,H,W) fp32, target of the same shape, uint8 {0,1} or fp32 in [0,1] ->
+    (loss () fp32 = BCELoss(sigmoid(logits), target) as a function of real numbers, dlogits (N,1,H,W) or None unless ``grad``,
+    inter (N) int32, union (N) int32: the counts behind mask_iou).  All on the device, deterministic, no host synchronisation."""
+    for name, t in (('logits', logits), ('target', target)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError('bce_logits: %s must be a tensor, got %s' % (name, type(t).__name__))
+        if not t.is_cuda:
+            raise RuntimeError('bce_logits: %s is on %s; the loss kernel runs on the GPU only (no CPU fallback)' % (name, t.device))
+    if logits.device != target.device:
+        raise ValueError('bce_logits: logits on %s, target on %s' % (logits.device, target.device))
+    if logits.dim() != 4 or logits.shape[1] != 1 or logits.numel() == 0:
+        raise ValueError('bce_logits: expected (N,1,H,W) logits, got %s' % (tuple(logits.shape),))
+    if tuple(target.shape) != tuple(logits.shape):
+        raise ValueError('bce_logits: logits %s and target %s differ in size' % (tuple(logits.shape), tuple(target.shape)))
+    if logits.dtype != torch.float32 or target.dtype not in (torch.float32, torch.uint8):
+        raise TypeError('bce_logits: expected fp32 logits and uint8 / fp32 targets, got %s and %s' % (logits.dtype, target.dtype))
+    N, _, Hh, Ww = logits.shape
+    z, t = _aligned16(logits.detach().contiguous()), _aligned16(target.detach().contiguous())
+    dev = z.device
+    dz = torch.empty_like(z) if grad else None
+    loss = torch.empty((), device=dev)
+    counts = torch.empty(2, N, dtype=torch.int32, device=dev)
+    ws = torch.empty(H.lib().frtm_bce_logits_workspace_bytes(N, Hh, Ww) // 8, dtype=torch.float64, device=dev)
+    H.call('frtm_bce_logits', H.ptr(z), H.ptr(t), t.element_size(), N, Hh, Ww, H.ptr(dz), H.ptr(loss), H.ptr(counts[0]), H.ptr(counts[1]),
+           H.ptr(ws), ws.numel() * 8)
+    return loss, dz, counts[0], counts[1]
+
+
+def adam_chunk_elems():
+    return H.lib().frtm_adam_chunk_elems()
+
+
+def adam_step(tensors, n_tensors, chunks, n_chunks, lr, bias_correction1, bias_correction2, beta1, beta2, eps, weight_decay, amsgrad):
+    """One launch of frtm_adam_amsgrad over the device tables ``tensors`` (int64, 8 words per tensor) and ``chunks`` (int32 pairs);
+    lib/fused_adam.py builds them."""
+    assert tensors.is_cuda and tensors.dtype == torch.int64 and tensors.numel() == 8 * n_tensors
+    assert chunks.is_cuda and chunks.dtype == torch.int32 and chunks.numel() == 2 * n_chunks
+    H.call('frtm_adam_amsgrad', H.ptr(tensors), int(n_tensors), H.ptr(chunks), int(n_chunks), float(lr), float(bias_correction1),
+           float(bias_correction2), float(beta1), float(beta2), float(eps), float(weight_decay), int(bool(amsgrad)))
+
+
+def scale_by_(x, scale):
+    """x *= scale in place, ``scale`` a one-element fp32 tensor on the device (frtm_scale_by): no read-back of the scalar."""
+    assert x.is_cuda and x.is_contiguous() and x.dtype == torch.float32 and scale.dtype == torch.float32 and scale.numel() == 1
+    H.call('frtm_scale_by', H.ptr(x), x.numel(), H.ptr(scale.contiguous()))
+    return x

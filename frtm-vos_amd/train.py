@@ -1,0 +1,98 @@
+"""Train the refiner (counterpart of the reference's train.py, its hyper-parameters wired onto this package's HIP training step).
+
+``python -m frtm_vos_amd.train NAME [--ftext resnet101|resnet18] [--dev cuda:0] [--dset synthetic] [--epochs N] [--batch-size B]
+[--workspace DIR]``
+
+Per batch: target models fitted on the augmented first frames on the HIP path (or read from the cache under the workspace), the
+refiner's forward and backward (``refiner_backend='hip'``), the loss tail (``loss_backend='hip'``) and the AMSGrad step (``FusedAdam``)
+on the project's kernels.  Recipe as the reference's: Adam, lr 1e-3, betas (0.9, 0.999), weight_decay 1e-5, amsgrad, StepLR(127, 0.1),
+batch 16, three frames per sample, a checkpoint per epoch under ``<workspace>/checkpoints/NAME/`` that ``evaluate.py --model`` reads.
+
+Only the synthetic sample sets exist here (lib/training_datasets.py): file-backed DAVIS / YouTube-VOS training sets are not implemented.
+"""
+import argparse
+from pathlib import Path
+
+import torch
+
+from .evaluate import AttrDict
+
+
+class ModelParameters:
+    """The training configuration of the reference (train.py:23-92): 15 augmentations of the first frame, a 32-channel target model
+    without pixel weighting, the 64-channel refiner with BatchNorm."""
+
+    def __init__(self, name, feature_extractor='resnet101', device='cuda:0', batch_size=None, tmodel_cache_path=None):
+        self.name, self.device, self.batch_size = name, device, batch_size
+        self.feature_extractor = feature_extractor
+        self.aug_params = AttrDict(
+            num_aug=15, min_px_count=1,
+            fg_aug_params=AttrDict(
+                rotation=[5, -5, 10, -10, 20, -20, 30, -30, 45, -45], fliplr=[False, False, False, False, True],
+                scale=[0.5, 0.7, 1.0, 1.5, 2.0, 2.5], skew=[(0.0, 0.0), (0.0, 0.0), (0.1, 0.1)],
+                blur_size=[0.0, 0.0, 0.0, 2.0], blur_angle=[0, 45, 90, 135]),
+            bg_aug_params=AttrDict(
+                tcenter=[(0.5, 0.5)], rotation=[0, 0, 0], fliplr=[False], scale=[1.0, 1.0, 1.2], skew=[(0.0, 0.0)],
+                blur_size=[0.0, 0.0, 1.0, 2.0, 5.0], blur_angle=[0, 45, 90, 135]))
+        self.disc_params = AttrDict(
+            layer='layer4', in_channels=256 if '18' in feature_extractor else 1024, c_channels=32, out_channels=1,
+            init_iters=(5, 10, 10, 10, 10), update_iters=(10,), update_filters=True,
+            filter_reg=(1e-5, 1e-4), precond=(1e-5, 1e-4), precond_lr=0.1, CG_forgetting_rate=75,
+            memory_size=20, train_skipping=8, learning_rate=0.1, pixel_weighting=None, device=device)
+        self.refnet_params = AttrDict(refinement_layers=('layer5', 'layer4', 'layer3', 'layer2'), nchannels=64, use_batch_norm=True)
+        self.tmodel_cache = AttrDict(enable=tmodel_cache_path is not None, read_only=False,
+                                     path=None if tmodel_cache_path is None else
+                                     Path(tmodel_cache_path) / ('%s-c%d' % (feature_extractor, self.disc_params.c_channels)))
+
+    def get_model(self):
+        from .model.augmenter import ImageAugmenter
+        from .model.feature_extractor import ResnetFeatureExtractor
+        from .model.seg_network import SegNetwork
+        from .model.training_model import TrainerModel
+        augmenter = ImageAugmenter(self.aug_params)
+        extractor = ResnetFeatureExtractor(self.feature_extractor).to(self.device)       # weights: FRTM_RESNET_WEIGHTS, else seeded synthetic ones
+        p = self.refnet_params
+        chans = {L: n for L, n in extractor.get_out_channels().items() if L in p.refinement_layers}
+        self.disc_params.in_channels = extractor.get_out_channels()[self.disc_params.layer]
+        torch.manual_seed(1)                                       # seeded default init, as evaluate.Parameters.make_refiner
+        refiner = SegNetwork(1, p.nchannels, chans, p.use_batch_norm).to(self.device)
+        return TrainerModel(augmenter, extractor, self.disc_params, refiner, batch_size=self.batch_size, tmodel_cache=self.tmodel_cache,
+                            device=self.device, refiner_backend='hip', loss_backend='hip')
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(description='Train the FRTM refiner (MI355X-native training step)')
+    ap.add_argument('name', help='name of the training session: checkpoint and log sub-directories')
+    ap.add_argument('--ftext', default='resnet101', choices=['resnet101', 'resnet18'], help='feature extractor')
+    ap.add_argument('--dev', default='cuda:0')
+    ap.add_argument('--dset', default='synthetic', choices=['synthetic'], help='training data (only synthetic sample sets are implemented)')
+    ap.add_argument('--epochs', type=int, default=260)
+    ap.add_argument('--batch-size', type=int, default=16)
+    ap.add_argument('--workspace', default='workspace', help='checkpoints/, logs/ and tmodels_cache/ are created below it')
+    ap.add_argument('--synthetic-sequences', type=int, default=32)
+    ap.add_argument('--synthetic-size', default='480x854', help='HxW of the synthetic frames')
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    from .lib.fused_adam import FusedAdam
+    from .lib.training import Trainer
+    from .lib.training_datasets import SyntheticTrainingDataset
+    args = parse_args(argv)
+    ws = Path(args.workspace).expanduser().resolve()
+    if torch.device(args.dev).type == 'cuda':
+        torch.cuda.set_device(torch.device(args.dev).index or 0)
+    size = tuple(int(v) for v in args.synthetic_size.lower().split('x'))
+    dataset = SyntheticTrainingDataset(n_sequences=args.synthetic_sequences, size=size, sample_size=3)
+    params = ModelParameters(args.name, feature_extractor=args.ftext, device=args.dev, tmodel_cache_path=ws / 'tmodels_cache',
+                             batch_size=args.batch_size)
+    model = params.get_model()
+    optimizer = FusedAdam(model.refiner.parameters(), lr=1e-3, betas=(0.9, 0.999), weight_decay=1e-5, amsgrad=True)
+    scheduler = torch.optim.lr_scheduler.StepLR(optimizer, step_size=127, gamma=0.1)
+    trainer = Trainer(args.name, model, optimizer, scheduler, dataset, checkpoints_path=ws / 'checkpoints', log_path=ws / 'logs',
+                      max_epochs=args.epochs, batch_size=args.batch_size, num_workers=0, load_latest=True, save_interval=1)
+    trainer.train()
+
+
+if __name__ == '__main__':
+    main()

@@ -592,6 +592,34 @@ size_t frtm_jf_workspace_bytes(int T, int H, int W, int K);
 int frtm_jf_counts(const void* pred, const void* truth, int label_bytes, int T, int H, int W, const int* ids, int K, int r, int* counts,
                    void* ws, size_t ws_bytes, frtm_stream_t stream);
 
+/* The loss tail of a refiner training step in one pass (csrc/train_step.hip; model/train_loss.py): BCELoss(sigmoid(z), t) as a function
+ * of real numbers.  logits: DEVICE z [N][1][H][W] fp32; target: DEVICE t of the same shape, target_bytes = 1 (uint8 {0,1}) or 4 (fp32
+ * in [0,1], soft targets allowed).  Outputs, all DEVICE: loss[1] = mean of t * min(softplus(-z), 100) + (1 - t) * min(softplus(z), 100)
+ * (fp32 terms, summed in fp64 in a fixed order: per-workgroup partials in ws, a second launch adds them, a wave per sample; no atomics);
+ * dlogits (may be NULL: evaluation only) = (sigmoid(z) - t) / (N H W), the part of a term whose clamp at 100 binds contributing nothing;
+ * inter[N] / uni[N] = int32 counts of (z > 0) & (t > 0.5) and (z > 0) | (t > 0.5) per sample (the inputs of mask_iou).
+ * logits, dlogits and fp32 targets must be 16-byte aligned (uint8 targets 4-byte); ws: frtm_bce_logits_workspace_bytes(N, H, W) bytes,
+ * 8-byte aligned.  N <= 65535. */
+size_t frtm_bce_logits_workspace_bytes(int N, int H, int W);
+int frtm_bce_logits(const float* logits, const void* target, int target_bytes, int N, int H, int W, float* dlogits, float* loss, int* inter,
+                    int* uni, void* ws, size_t ws_bytes, frtm_stream_t stream);
+
+/* x[i] *= scale[0] for n floats, scale a DEVICE scalar (the loss's incoming gradient applied to dlogits without a host read-back).
+ * x 16-byte aligned. */
+int frtm_scale_by(float* x, size_t n, const float* scale, frtm_stream_t stream);
+
+/* torch.optim.Adam's update for one parameter group in one launch (csrc/train_step.hip; lib/fused_adam.py), per element in fp32:
+ *   g += wd * p;  m = b1 m + (1 - b1) g;  v = b2 v + (1 - b2) g g;  vmax = max(vmax, v)  [amsgrad];
+ *   p -= (lr / bias_correction1) * m / (sqrt(vmax or v) / sqrt(bias_correction2) + eps).
+ * tensors: DEVICE table, eight 64-bit words per tensor = pointers p, grad, exp_avg, exp_avg_sq, max_exp_avg_sq (ignored unless amsgrad),
+ * element count, 1 if all five pointers are 16-byte aligned (else the tensor is walked element by element), 0.  chunks: DEVICE int32
+ * pairs (tensor index, chunk index): chunk c of a tensor is its elements [c * E, min((c + 1) * E, count)), E = frtm_adam_chunk_elems();
+ * every tensor needs ceil(count / E) chunks.  Pairs outside the table are skipped.  The scalars are launch arguments: a learning-rate
+ * schedule changes no table. */
+int frtm_adam_chunk_elems(void);
+int frtm_adam_amsgrad(const void* tensors, int ntensors, const void* chunks, int nchunks, double lr, double bias_correction1,
+                      double bias_correction2, double beta1, double beta2, double eps, double weight_decay, int amsgrad, frtm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
