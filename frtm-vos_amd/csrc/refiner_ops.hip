@@ -613,6 +613,7 @@ extern "C" {
 
 int frtm_tap_mix(const float* y, int n, int C, int hw, const float* w3x3, float* out, frtm_stream_t stream) {
   FRTM_CHECK_ARG(y && w3x3 && out && n > 0 && C > 0 && hw > 0, "frtm_tap_mix: bad argument");
+  FRTM_CHECK_ARG(n <= 65535, "frtm_tap_mix: at most 65535 samples per call (got %d)", n);
   if (hw % 4 == 0 && ((size_t)y % 16 == 0) && ((size_t)out % 16 == 0))
     k_tap_mix<4><<<dim3(ceil_div(hw / 4, 256), n), 256, 0, (hipStream_t)stream>>>(y, w3x3, C, hw / 4, out);
   else
@@ -623,7 +624,9 @@ int frtm_tap_mix(const float* y, int n, int C, int hw, const float* w3x3, float*
 
 int frtm_bilinear_resize(const float* in, int planes, int h, int w, float* out, int H, int W, frtm_stream_t stream) {
   FRTM_CHECK_ARG(in && out && planes > 0 && h > 0 && w > 0 && H > 0 && W > 0, "frtm_bilinear_resize: bad argument");
+  FRTM_CHECK_ARG((size_t)H * W < 0x7fffffff && (size_t)h * w < 0x7fffffff, "frtm_bilinear_resize: map too large");
   const int ppz = 8;
+  FRTM_CHECK_ARG(ceil_div(planes, ppz) <= 65535, "frtm_bilinear_resize: at most %d planes per call (got %d)", 65535 * ppz, planes);
   dim3 g(ceil_div(H * W, 256), ceil_div(planes, ppz));
   k_bilinear_resize<<<g, 256, 0, (hipStream_t)stream>>>(in, h, w, out, H, W, planes, ppz);
   FRTM_LAUNCH_CHECK();
@@ -633,6 +636,10 @@ int frtm_bilinear_resize(const float* in, int planes, int h, int w, float* out, 
 int frtm_tse_inject(const float* base, const float* bias, const float* ws, const float* scores, int n, int group, int C, int h, int w, int H,
                     int W, float* out, frtm_stream_t stream) {
   FRTM_CHECK_ARG(base && bias && ws && scores && out && n > 0 && C > 0 && group > 0 && n % group == 0, "frtm_tse_inject: bad argument");
+  FRTM_CHECK_ARG(h > 0 && w > 0 && H > 0 && W > 0, "frtm_tse_inject: map sizes must be positive (scores %d x %d, maps %d x %d)", h, w, H, W);
+  FRTM_CHECK_ARG((size_t)H * W < 0x7fffffff && (size_t)h * w < 0x7fffffff, "frtm_tse_inject: map too large");
+  FRTM_CHECK_ARG((size_t)n * INJ_CG <= 65535, "frtm_tse_inject: at most %d samples per call (got %d)", 65535 / INJ_CG, n);
+  FRTM_CHECK_ARG(ceil_div(H, INJ_TH) <= 65535, "frtm_tse_inject: at most %d rows per map (got %d)", 65535 * INJ_TH, H);
   dim3 g(ceil_div(W, INJ_TW), ceil_div(H, INJ_TH), n * INJ_CG);
   k_tse_inject<<<g, 256, 0, (hipStream_t)stream>>>(base, bias, ws, scores, C, h, w, H, W, out, group);
   FRTM_LAUNCH_CHECK();
@@ -642,6 +649,8 @@ int frtm_tse_inject(const float* base, const float* bias, const float* ws, const
 int frtm_cab_combine(const float* shallow, const float* gate, const float* deeper, int n, int C, int hd, int wd, int deeper_group, int H,
                      int W, float* out, frtm_stream_t stream) {
   FRTM_CHECK_ARG(shallow && gate && deeper && out && n > 0 && C > 0 && deeper_group >= 0, "frtm_cab_combine: bad argument");
+  FRTM_CHECK_ARG(hd > 0 && wd > 0 && H > 0 && W > 0, "frtm_cab_combine: map sizes must be positive (deeper %d x %d, maps %d x %d)", hd, wd, H, W);
+  FRTM_CHECK_ARG(deeper_group == 0 || n % deeper_group == 0, "frtm_cab_combine: %d samples are not a multiple of deeper_group %d", n, deeper_group);
   FRTM_CHECK_ARG((size_t)n * C <= 65535 && (size_t)H * W < 0x7fffffff, "frtm_cab_combine: at most 65535 planes per call");
   dim3 g(ceil_div(H, CAB_RB), n * C);
   k_cab_combine<<<g, 256, 0, (hipStream_t)stream>>>(shallow, gate, deeper, C, hd, wd, deeper_group, H, W, out);
@@ -651,7 +660,12 @@ int frtm_cab_combine(const float* shallow, const float* gate, const float* deepe
 
 int frtm_cab_gate(const float* sp, const float* dp, int dp_group, const float* W1, const float* b1, const float* W2, const float* b2,
                   int n, int oc, float* gate, frtm_stream_t stream) {
-  FRTM_CHECK_ARG(sp && dp && W1 && b1 && W2 && b2 && gate && n > 0 && oc > 0 && oc <= 4096, "frtm_cab_gate: bad argument");
+  FRTM_CHECK_ARG(sp && dp && W1 && b1 && W2 && b2 && gate && n > 0 && oc > 0, "frtm_cab_gate: bad argument");
+  FRTM_CHECK_ARG(dp_group >= 0, "frtm_cab_gate: dp_group must not be negative (got %d)", dp_group);
+  // 7 oc floats of dynamic LDS; 64 KB is what a launch gets without raising the kernel's limit
+  FRTM_CHECK_ARG((size_t)7 * oc * sizeof(float) <= 65536, "frtm_cab_gate: oc = %d needs %zu bytes of LDS, more than the 65536 of a default launch",
+                 oc, (size_t)7 * oc * sizeof(float));
+  FRTM_CHECK_ARG(dp_group == 0 || n % dp_group == 0, "frtm_cab_gate: %d samples are not a multiple of dp_group %d", n, dp_group);
   FRTM_CHECK_ARG(oc % 4 == 0, "frtm_cab_gate: oc must be a multiple of 4 (got %d)", oc);
   k_cab_gate<<<n, 256, 7 * oc * sizeof(float), (hipStream_t)stream>>>(sp, dp, dp_group, W1, b1, W2, b2, oc, gate);
   FRTM_LAUNCH_CHECK();
@@ -669,6 +683,7 @@ int frtm_pyrup2x(const float* in, int planes, int h, int w, float* out, frtm_str
 int frtm_project_tail(const float* y, int n, int C, int h, int w, const float* w3x3, const float* bias, int Ho, int Wo, float* out,
                       frtm_stream_t stream) {
   FRTM_CHECK_ARG(y && w3x3 && out && n > 0 && C > 0 && h > 1 && w > 1 && Ho > 0 && Wo > 0, "frtm_project_tail: bad argument");
+  FRTM_CHECK_ARG(n <= 65535, "frtm_project_tail: at most 65535 samples per call (got %d)", n);
   // LDS patch bounds: the rows / columns of the 2x-upsampled map a 16x64 output tile (+1 halo) reads through the bilinear taps
   const double sy = 2.0 * h / Ho, sx = 2.0 * w / Wo;
   FRTM_CHECK_ARG((int)(PT_ZR * sy) + 3 <= PT_UR && (int)(PT_ZC * sx) + 3 <= PT_UC,
