@@ -139,6 +139,8 @@ SIGNATURES = {
     'frtm_scale_by': (I, [P, ctypes.c_size_t, P, P]),
     'frtm_adam_chunk_elems': (I, []),
     'frtm_adam_amsgrad': (I, [P, I, P, I, D, D, D, D, D, D, D, I, P]),
+    'frtm_resize_frames_u8': (I, [P, ctypes.c_size_t, P, P, I, I, P, I, I, P]),
+    'frtm_resize_labels_u8': (I, [P, ctypes.c_size_t, P, P, I, P, I, I, P]),
 }
 
 _lib = None

@@ -37,8 +37,10 @@ class Trainer:
 
     def __init__(self, name, model, optimizer, scheduler, dataset, checkpoints_path, log_path, max_epochs, batch_size, num_workers=0,
                  load_latest=True, save_interval=5, stats_to_print=('stats/loss', 'stats/accuracy', 'stats/lr', 'stats/fcache_hits'),
-                 seed=0):
-        """dataset: one sample-set dataset (lib/training_datasets.py) or a list of them (concatenated)."""
+                 seed=0, collate_fn=None, batch_transform=None):
+        """dataset: one sample-set dataset (lib/training_datasets.py) or a list of them (concatenated).
+        collate_fn: the DataLoader's collate step (None: the default one); batch_transform: a callable applied to every collated batch
+        before ``model(*batch)`` (None: the batch as it is).  The file-backed sample sets need both: raw_collate and a DeviceFrameResizer."""
         self.name, self.model, self.optimizer, self.scheduler = name, model, optimizer, scheduler
         self.datasets = list(dataset) if isinstance(dataset, (list, tuple)) else [dataset]
         self.checkpoints_path = Path(checkpoints_path) / name
@@ -47,6 +49,7 @@ class Trainer:
         self.epoch = 0
         self.max_epochs, self.batch_size, self.num_workers, self.save_interval = int(max_epochs), int(batch_size), int(num_workers), int(save_interval)
         self.stats_to_print, self.seed = tuple(stats_to_print), int(seed)
+        self.collate_fn, self.batch_transform = collate_fn, batch_transform
         self.stats = {}
         self._tb = None
         if load_latest:
@@ -80,7 +83,7 @@ class Trainer:
                 d.set_epoch(epoch)
         dset = self.datasets[0] if len(self.datasets) == 1 else ConcatDataset(self.datasets)
         return DataLoader(dset, batch_size=self.batch_size, num_workers=self.num_workers, shuffle=True, pin_memory=torch.cuda.is_available(),
-                          generator=epoch_generator(self.seed, epoch, stream=1))
+                          generator=epoch_generator(self.seed, epoch, stream=1), collate_fn=self.collate_fn)
 
     def _log(self, seconds):
         self.log_path.mkdir(exist_ok=True, parents=True)
@@ -104,6 +107,8 @@ class Trainer:
             t_epoch = t0 = time.time()
             for i, batch in enumerate(loader, 1):
                 self.optimizer.zero_grad()
+                if self.batch_transform is not None:
+                    batch = self.batch_transform(batch)
                 stats = dict(self.model(*batch))
                 self.optimizer.step()
                 stats['stats/lr'] = self.scheduler.get_last_lr()[0]

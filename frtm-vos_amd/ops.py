@@ -348,3 +348,39 @@ def scale_by_(x, scale):
     assert x.is_cuda and x.is_contiguous() and x.dtype == torch.float32 and scale.dtype == torch.float32 and scale.numel() == 1
     H.call('frtm_scale_by', H.ptr(x), x.numel(), H.ptr(scale.contiguous()))
     return x
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# Batched resize of native-size training frames and label maps (csrc/frame_resize.hip; lib/training_datasets.py: DeviceFrameResizer)
+# ----------------------------------------------------------------------------------------------------------------------
+RESIZE_MODES = {'area': 0, 'cubic': 1}
+
+
+def _resize_packed(entry, src, desc, planes, size):
+    if not isinstance(src, torch.Tensor) or not src.is_cuda:
+        raise RuntimeError('%s: the packed source is on %s; the resize kernels run on the GPU only (no CPU fallback)'
+                           % (entry, getattr(src, 'device', type(src).__name__)))
+    if src.dtype != torch.uint8 or src.dim() != 1:
+        raise TypeError('%s: expected a flat uint8 buffer, got %s %s' % (entry, src.dtype, tuple(src.shape)))
+    if not isinstance(desc, torch.Tensor) or desc.is_cuda or desc.dtype != torch.int64 or desc.dim() != 2 or desc.shape[1] != 4 or desc.shape[0] < 1:
+        raise TypeError('%s: the frame table is a CPU int64 tensor of shape (n, 4), n >= 1' % entry)
+    desc = desc.contiguous()
+    n = desc.shape[0]
+    out = torch.empty(n, planes, int(size[0]), int(size[1]), dtype=torch.uint8, device=src.device)
+    table = H.upload(desc, src.device)
+    args = (H.ptr(src), src.numel(), desc.data_ptr(), H.ptr(table), n) + ((planes,) if entry == 'frtm_resize_frames_u8' else ())
+    H.call(entry, *args, H.ptr(out), int(size[0]), int(size[1]))
+    return out
+
+
+def resize_frames_u8(src, desc, planes, size):
+    """frtm_resize_frames_u8: ``src`` a flat uint8 device buffer of frames packed at any byte offsets, ``desc`` a CPU int64 (n,4) table
+    of rows (offset, h, w, RESIZE_MODES[mode]), each frame ``planes`` planes of h x w bytes -> (n, planes, H, W) uint8 on the device.
+    One launch, enqueued on the current stream."""
+    return _resize_packed('frtm_resize_frames_u8', src, desc, int(planes), size)
+
+
+def resize_labels_u8(src, desc, size):
+    """frtm_resize_labels_u8: label maps packed like the frames (one plane each), ``desc`` rows (offset, h, w, obj_id) -> (n, 1, H, W)
+    uint8 = (label == obj_id) at F.interpolate(mode='nearest')'s source indices.  One launch, enqueued on the current stream."""
+    return _resize_packed('frtm_resize_labels_u8', src, desc, 1, size)

@@ -1,14 +1,18 @@
 """Train the refiner (counterpart of the reference's train.py, its hyper-parameters wired onto this package's HIP training step).
 
-``python -m frtm_vos_amd.train NAME [--ftext resnet101|resnet18] [--dev cuda:0] [--dset synthetic] [--epochs N] [--batch-size B]
-[--workspace DIR]``
+``python -m frtm_vos_amd.train NAME [--ftext resnet101|resnet18] [--dev cuda:0] [--dset synthetic|davis|ytvos|davis+ytvos]
+[--davis-path DIR] [--ytvos-path DIR] [--ytvos-sequences-file FILE] [--occlusion-overrides FILE] [--num-workers N] [--epochs N]
+[--batch-size B] [--workspace DIR]``
 
 Per batch: target models fitted on the augmented first frames on the HIP path (or read from the cache under the workspace), the
 refiner's forward and backward (``refiner_backend='hip'``), the loss tail (``loss_backend='hip'``) and the AMSGrad step (``FusedAdam``)
 on the project's kernels.  Recipe as the reference's: Adam, lr 1e-3, betas (0.9, 0.999), weight_decay 1e-5, amsgrad, StepLR(127, 0.1),
 batch 16, three frames per sample, a checkpoint per epoch under ``<workspace>/checkpoints/NAME/`` that ``evaluate.py --model`` reads.
 
-Only the synthetic sample sets exist here (lib/training_datasets.py): file-backed DAVIS / YouTube-VOS training sets are not implemented.
+``--dset synthetic`` (the default) trains on generated clips and needs no files.  ``davis``, ``ytvos`` and ``davis+ytvos`` read DAVIS 2017
+train / YouTube-VOS train from disk (lib/training_datasets.py): frames are decoded at their native size by the loader and resized to
+480 x 854 on the device, a batch per launch (csrc/frame_resize.hip); the occlusion tables are computed on first use and kept under
+``<workspace>/meta/``.
 """
 import argparse
 from pathlib import Path
@@ -65,7 +69,12 @@ def parse_args(argv=None):
     ap.add_argument('name', help='name of the training session: checkpoint and log sub-directories')
     ap.add_argument('--ftext', default='resnet101', choices=['resnet101', 'resnet18'], help='feature extractor')
     ap.add_argument('--dev', default='cuda:0')
-    ap.add_argument('--dset', default='synthetic', choices=['synthetic'], help='training data (only synthetic sample sets are implemented)')
+    ap.add_argument('--dset', default='synthetic', choices=['synthetic', 'davis', 'ytvos', 'davis+ytvos'], help='training data')
+    ap.add_argument('--davis-path', default=None, help='DAVIS root (JPEGImages/480p, Annotations/480p, ImageSets/2017/train.txt)')
+    ap.add_argument('--ytvos-path', default=None, help='YouTube-VOS root (train/JPEGImages, train/Annotations)')
+    ap.add_argument('--ytvos-sequences-file', default=None, help='YouTube-VOS sequence ids to train on, one per line (default: all)')
+    ap.add_argument('--occlusion-overrides', default=None, help='JSON file of per-sequence DAVIS occlusion overrides')
+    ap.add_argument('--num-workers', type=int, default=0, help='DataLoader workers (decoding; the resize runs on the device)')
     ap.add_argument('--epochs', type=int, default=260)
     ap.add_argument('--batch-size', type=int, default=16)
     ap.add_argument('--workspace', default='workspace', help='checkpoints/, logs/ and tmodels_cache/ are created below it')
@@ -74,23 +83,47 @@ def parse_args(argv=None):
     return ap.parse_args(argv)
 
 
+def file_datasets(args, workspace):
+    """The file-backed sample sets ``--dset`` names, with the reference's epoch sizes (train.py:123-125: DAVIS 8 repeats, YouTube-VOS
+    4000 samples)."""
+    from .lib.training_datasets import DAVISDataset, YouTubeVOSDataset, default_meta_file
+    out = []
+    for kind in args.dset.split('+'):
+        path = {'davis': args.davis_path, 'ytvos': args.ytvos_path}[kind]
+        if path is None:
+            raise SystemExit('--dset %s needs --%s-path' % (args.dset, kind))
+        if kind == 'davis':
+            out.append(DAVISDataset(path, epoch_repeats=8, sample_size=3, meta_file=default_meta_file('davis', workspace),
+                                    overrides=args.occlusion_overrides))
+        else:
+            out.append(YouTubeVOSDataset(path, epoch_samples=4000, sample_size=3, meta_file=default_meta_file('ytvos2018', workspace),
+                                         sequences_file=args.ytvos_sequences_file))
+    return out
+
+
 def main(argv=None):
     from .lib.fused_adam import FusedAdam
     from .lib.training import Trainer
-    from .lib.training_datasets import SyntheticTrainingDataset
+    from .lib.training_datasets import DeviceFrameResizer, SyntheticTrainingDataset, raw_collate
     args = parse_args(argv)
     ws = Path(args.workspace).expanduser().resolve()
     if torch.device(args.dev).type == 'cuda':
         torch.cuda.set_device(torch.device(args.dev).index or 0)
-    size = tuple(int(v) for v in args.synthetic_size.lower().split('x'))
-    dataset = SyntheticTrainingDataset(n_sequences=args.synthetic_sequences, size=size, sample_size=3)
+    hooks = {}
+    if args.dset == 'synthetic':
+        size = tuple(int(v) for v in args.synthetic_size.lower().split('x'))
+        dataset = SyntheticTrainingDataset(n_sequences=args.synthetic_sequences, size=size, sample_size=3)
+    else:
+        dataset = file_datasets(args, ws)
+        hooks = dict(collate_fn=raw_collate, batch_transform=DeviceFrameResizer((480, 854), args.dev, datasets=dataset))
     params = ModelParameters(args.name, feature_extractor=args.ftext, device=args.dev, tmodel_cache_path=ws / 'tmodels_cache',
                              batch_size=args.batch_size)
     model = params.get_model()
     optimizer = FusedAdam(model.refiner.parameters(), lr=1e-3, betas=(0.9, 0.999), weight_decay=1e-5, amsgrad=True)
     scheduler = torch.optim.lr_scheduler.StepLR(optimizer, step_size=127, gamma=0.1)
     trainer = Trainer(args.name, model, optimizer, scheduler, dataset, checkpoints_path=ws / 'checkpoints', log_path=ws / 'logs',
-                      max_epochs=args.epochs, batch_size=args.batch_size, num_workers=0, load_latest=True, save_interval=1)
+                      max_epochs=args.epochs, batch_size=args.batch_size, num_workers=args.num_workers, load_latest=True, save_interval=1,
+                      **hooks)
     trainer.train()
 
 

@@ -620,6 +620,26 @@ int frtm_adam_chunk_elems(void);
 int frtm_adam_amsgrad(const void* tensors, int ntensors, const void* chunks, int nchunks, double lr, double bias_correction1,
                       double bias_correction2, double beta1, double beta2, double eps, double weight_decay, int amsgrad, frtm_stream_t stream);
 
+/* Batched resize of native-size uint8 training frames / label maps to the training size in one launch each (csrc/frame_resize.hip;
+ * replaces the per-frame cv2.resize / F.interpolate of the reference's lib/training_datasets.py:185-195, which run on the CPU).
+ * src: DEVICE byte buffer of src_bytes bytes holding n frames one after another at ARBITRARY byte offsets (no alignment is asked of the
+ * packer or of src itself).  The table has one row of four 64-bit words per frame and is passed twice: desc_host (HOST memory, checked
+ * before the launch: 1 <= h, w <= 16384, the frame inside the buffer, a known mode / an id in 0..255 -- anything else returns
+ * FRTM_ERR_ARG without launching) and desc_dev, the same rows in DEVICE memory, which the kernel reads.  1 <= H, W <= 16384.
+ *   frtm_resize_frames_u8   rows {offset, h, w, mode}; a frame is `planes` planes of h x w bytes; out (n, planes, H, W) uint8;
+ *                           n * planes <= 65535.  FRTM_RESIZE_AREA (cv2.INTER_AREA's role), per axis: src > dst: the mean over the source
+ *                           interval [d src/dst, (d + 1) src/dst) with fractional edge coverage; src == dst: the identity (bit-exact);
+ *                           src < dst: bilinear, half-pixel centres, replicate border.  FRTM_RESIZE_CUBIC: frtm_bicubic_resize's operator.
+ *                           fp32 sums with weights one rounding away from exact, ONE rounding to nearest-even, clamp to 0..255.
+ *   frtm_resize_labels_u8   rows {offset, h, w, obj_id}; a frame is one plane; out (n, 1, H, W) uint8 = (src == obj_id) at the source
+ *                           index of F.interpolate(mode='nearest'): min(floor(dst * (float(src) / dst_size)), src - 1) in float32. */
+#define FRTM_RESIZE_AREA 0
+#define FRTM_RESIZE_CUBIC 1
+int frtm_resize_frames_u8(const unsigned char* src, size_t src_bytes, const long long* desc_host, const long long* desc_dev, int n, int planes,
+                          unsigned char* out, int H, int W, frtm_stream_t stream);
+int frtm_resize_labels_u8(const unsigned char* src, size_t src_bytes, const long long* desc_host, const long long* desc_dev, int n,
+                          unsigned char* out, int H, int W, frtm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
