@@ -19,6 +19,7 @@ struct ConvL {
   float* wW4 = nullptr;         // ... with >= 128 channels: third image, the 36 matrices of Winograd F(4x4,3x3) (FRTM_WLAYOUT_WINO4)
   float* wW6 = nullptr;         // ... and the 64 matrices of F(6x6,3x3) (FRTM_WLAYOUT_WINO6)
   float* wB = nullptr;          // convs a bf16x3 trunk routes (bf16x3_packs), bf16x3 trunks only: the three bf16 pieces (FRTM_WLAYOUT_BF16X3), packed lazily
+  float* wB1 = nullptr;         // convs a bf16x1 trunk routes (bf16x1_packs), bf16x1 trunks only: one bf16 plane (FRTM_WLAYOUT_BF16X1), packed lazily
   bool loaded = false;
   int layout = 0;
   // per-conv launch plan (frtm_backbone_set_conv_plan; 0 = the planner's choice): the GEMM tile of the path the conv takes (direct 1x1 /
@@ -56,7 +57,9 @@ struct frtm_backbone {
   int use_winograd4 = getenv("FRTM_NO_WINO4") ? 0 : getenv("FRTM_NO_WINO6") ? 1 : 2;
   // fewest 64x64 product tiles for which the three-launch forms are taken (256 = one per CU: measured at batch 1 -- the streaming path -- 2.49 -> 2.23 ms per trunk pass; FRTM_WINO4_MIN_TILES)
   int wino4_min_tiles = getenv("FRTM_WINO4_MIN_TILES") ? atoi(getenv("FRTM_WINO4_MIN_TILES")) : 256;
-  int precision = 0;           // frtm_backbone_set_precision: 0 = fp32, 1 = bf16x3 for the routed stride-1 1x1 convs (bf16x3_route)
+  int precision = 0;           // frtm_backbone_set_precision / _set_bf16_pieces: 0 = fp32, 1 = bf16x3 for the routed stride-1 1x1 convs (bf16x3_route), 2 = bf16x1 (bf16x1_route)
+  // FRTM_BF16X1_MIN_COLS=n (tests and measurements on small frames): a bf16x1 trunk routes EVERY eligible conv from n columns per launch on, instead of the measured table
+  int bf16x1_min_cols = getenv("FRTM_BF16X1_MIN_COLS") ? atoi(getenv("FRTM_BF16X1_MIN_COLS")) : -1;
   int generation = 0;          // bumped whenever an arena / workspace is (re)allocated: captured graphs of older generations are stale
 };
 
@@ -194,6 +197,42 @@ static int pack_bf16x3(ConvL& c, hipStream_t st) {
   return frtm_bf16x3_pack(c.wT, c.Cout, c.Cin, 1, (c.Cout + 31) / 32 * 32, c.wB, st);
 }
 
+int frtm_bf16x1_pack(const float* src, int Cout, int Cin, int sm, int sk, float* out, hipStream_t st);
+
+// The convs a bf16x1 trunk sends to the bf16x1 kernel (csrc/conv_bf16x1.hip): only where its median measured faster than the fp32 form the conv would
+// otherwise take by more than the spread (max - min over the alternating rounds) of the fp32 arm in the same run, per shape and columns of the launch
+// (tools/bf16x1_trunk_time.py -> profiles/bf16x1_trunk_time.txt, on 480x854 frames at 1 and 8 frames per launch).  A shape measured faster at 8
+// frames only is routed from its 8-frame column count on; one faster at 1 frame as well, from its 1-frame column count on.  Shapes that were not
+// measured (the conv1 of a stage's first block: 64 -> 64, 256 -> 128, 512 -> 256, 1024 -> 512), or were not faster, stay fp32.
+// us per launch, fp32 / bf16x1 (automatic tile form), from that file:            1 frame          8 frames
+struct Bf16x1Rule { int Cin, Cout; long min_cols; };
+static const Bf16x1Rule kBf16x1Rules[] = {
+  {256, 1024, 1620},      // layer3 conv3, 30x54                                  13.3 / 10.0      58.6 / 41.1
+  {1024, 256, 1620},      // layer3 conv1                                         18.8 / 15.1      67.5 / 24.7
+  {128, 512, 6420},       // layer2 conv3, 60x107                                 14.2 / 11.4      67.6 / 65.0
+  {512, 128, 6420},       // layer2 conv1                                         13.9 / 11.0      56.7 / 31.9
+  {512, 2048, 405},       // layer4 conv3, 15x27                                  20.4 / 11.6      71.9 / 33.3
+  {2048, 512, 3240},      // layer4 conv1: slower at 1 frame                      22.3 / 27.6      92.3 / 33.6
+  {256, 64, 25680},       // layer1 conv1, 120x214                                13.2 /  9.7      59.8 / 48.1
+  // 64 -> 256 (layer1 conv3 and downsample, K = 64: one chunk, nothing to pipeline)  14.2 / 17.2     114.7 / 139.1: stays fp32
+};
+static const Bf16x1Rule* bf16x1_rule(const ConvL& c) {
+  for (const Bf16x1Rule& r : kBf16x1Rules)
+    if (r.Cin == c.Cin && r.Cout == c.Cout) return &r;
+  return nullptr;
+}
+static bool bf16x1_packs(const frtm_backbone* bb, const ConvL& c) { return bf16x3_eligible(c) && (bb->bf16x1_min_cols >= 0 || bf16x1_rule(c)); }
+static bool bf16x1_route(const frtm_backbone* bb, const ConvL& c, int B, int Ho, int Wo) {
+  if (!bf16x1_packs(bb, c)) return false;
+  const long cols = (long)B * Ho * Wo;
+  return cols >= (bb->bf16x1_min_cols >= 0 ? (long)bb->bf16x1_min_cols : bf16x1_rule(c)->min_cols);
+}
+
+static int pack_bf16x1(ConvL& c, hipStream_t st) {
+  if (!c.wB1) FRTM_HIP(hipMalloc((void**)&c.wB1, FRTM_CONV_BF16X1_ELEMS(c.Cout, c.Cin) * sizeof(float)));
+  return frtm_bf16x1_pack(c.wT, c.Cout, c.Cin, 1, (c.Cout + 31) / 32 * 32, c.wB1, st);
+}
+
 static int run_conv(frtm_backbone* bb, Lane& ln, int idx, int B, int Hin, int Win, const float* in, const float* residual, int relu,
                     float* out, int* Ho, int* Wo, hipStream_t st, int pad_override = -1) {
   ConvL& c = bb->convs[idx];
@@ -261,6 +300,11 @@ static int run_conv(frtm_backbone* bb, Lane& ln, int idx, int B, int Hin, int Wi
     d.w_layout = FRTM_WLAYOUT_BF16X3;
     d.splitk = 1;
     return frtm_conv2d(&d, in, c.wB, nullptr, c.scale, c.shift, residual, out, nullptr, st);
+  }
+  if (bb->precision == 2 && c.wB1 && !c.plan_tile && !c.plan_splitk && bf16x1_route(bb, c, B, *Ho, *Wo)) {
+    d.w_layout = FRTM_WLAYOUT_BF16X1;
+    d.splitk = 1;
+    return frtm_conv2d(&d, in, c.wB1, nullptr, c.scale, c.shift, residual, out, nullptr, st);
   }
   d.tile = c.plan_tile ? c.plan_tile : scanned_tile(c, B, *Ho, *Wo, false);
   d.splitk = c.plan_splitk;
@@ -424,6 +468,7 @@ int frtm_backbone_destroy(frtm_backbone_t* bb) {
     if (c.wW4) (void)hipFree(c.wW4);
     if (c.wW6) (void)hipFree(c.wW6);
     if (c.wB) (void)hipFree(c.wB);
+    if (c.wB1) (void)hipFree(c.wB1);
     if (c.scale) (void)hipFree(c.scale);
     if (c.shift) (void)hipFree(c.shift);
     if (c.ktab) (void)hipFree(c.ktab);
@@ -477,6 +522,10 @@ int frtm_backbone_set_conv(frtm_backbone_t* bb, int idx, const float* w_oihw, co
     rc = pack_bf16x3(c, st);
     if (rc) return rc;
   }
+  if (bf16x1_packs(bb, c) && (c.wB1 || bb->precision == 2)) {
+    rc = pack_bf16x1(c, st);
+    if (rc) return rc;
+  }
   if (c.ks == 3 && c.stride == 1 && c.pad == 1) {
     if (!c.wW) FRTM_HIP(hipMalloc((void**)&c.wW, (size_t)FRTM_CONV_WINO_ELEMS(c.Cout, c.Cin) * sizeof(float)));
     rc = frtm_conv_pack_weights(w_oihw, c.Cout, c.Cin, 3, FRTM_WLAYOUT_WINO3X3, c.wW, nullptr, stream);
@@ -507,16 +556,16 @@ int frtm_backbone_set_winograd(frtm_backbone_t* bb, int enable) {
   return FRTM_OK;
 }
 
-int frtm_backbone_set_precision(frtm_backbone_t* bb, int mode) {
-  FRTM_CHECK_ARG(bb, "frtm_backbone_set_precision: null handle");
-  FRTM_CHECK_ARG(mode == 0 || mode == 1, "frtm_backbone_set_precision: mode must be 0 (fp32) or 1 (bf16x3), got %d", mode);
+// mode: 0 = fp32, 1 = bf16x3, 2 = bf16x1 (the values of frtm_backbone::precision)
+static int set_precision_mode(frtm_backbone* bb, int mode) {
+  auto wants = [&](const ConvL& c) { return c.loaded && ((mode == 1 && bf16x3_packs(c) && !c.wB) || (mode == 2 && bf16x1_packs(bb, c) && !c.wB1)); };
   bool pack = false;
-  for (auto& c : bb->convs) pack |= mode == 1 && c.loaded && bf16x3_packs(c) && !c.wB;
-  if (pack) {            // a configuration call, not a stream operation: the GEMM images may come from any stream, and the split ones are ready on return
+  for (auto& c : bb->convs) pack |= wants(c);
+  if (pack) {            // a configuration call, not a stream operation: the GEMM images may come from any stream, and the bf16 ones are ready on return
     FRTM_HIP(hipDeviceSynchronize());
     for (auto& c : bb->convs)
-      if (c.loaded && bf16x3_packs(c) && !c.wB) {
-        int rc = pack_bf16x3(c, nullptr);
+      if (wants(c)) {
+        int rc = mode == 1 ? pack_bf16x3(c, nullptr) : pack_bf16x1(c, nullptr);
         if (rc) return rc;
       }
     FRTM_HIP(hipDeviceSynchronize());
@@ -524,6 +573,18 @@ int frtm_backbone_set_precision(frtm_backbone_t* bb, int mode) {
   if (mode != bb->precision) bb->generation += 1;       // captured graphs hold the other kernels
   bb->precision = mode;
   return FRTM_OK;
+}
+
+int frtm_backbone_set_precision(frtm_backbone_t* bb, int mode) {
+  FRTM_CHECK_ARG(bb, "frtm_backbone_set_precision: null handle");
+  FRTM_CHECK_ARG(mode == 0 || mode == 1, "frtm_backbone_set_precision: mode must be 0 (fp32) or 1 (bf16x3), got %d", mode);
+  return set_precision_mode(bb, mode);
+}
+
+int frtm_backbone_set_bf16_pieces(frtm_backbone_t* bb, int pieces) {
+  FRTM_CHECK_ARG(bb, "frtm_backbone_set_bf16_pieces: null handle");
+  FRTM_CHECK_ARG(pieces == 0 || pieces == 1 || pieces == 3, "frtm_backbone_set_bf16_pieces: pieces must be 0 (fp32), 1 (bf16x1) or 3 (bf16x3), got %d", pieces);
+  return set_precision_mode(bb, pieces == 3 ? 1 : pieces == 1 ? 2 : 0);
 }
 
 int frtm_backbone_set_winograd4(frtm_backbone_t* bb, int enable) {

@@ -23,9 +23,9 @@ class Parameters:
     def __init__(self, weights=None, fast=False, device='cuda:0', feature_extractor=None, backbone_weights=None, feature_batch=16, trunk_lanes=2,
                  ytvos_fork_solver=False, refiner_graphs=None, aug_fill='telea', upsampler='compat', trunk_precision='fp32'):
         self.device = device
-        if trunk_precision not in ('fp32', 'bf16x3'):
-            raise ValueError("trunk_precision must be 'fp32' or 'bf16x3', got %r" % (trunk_precision,))
-        self.trunk_precision = trunk_precision    # 'fp32' or 'bf16x3': the trunk's stride-1 1x1 convs on bf16 pieces (ResnetFeatureExtractor.precision)
+        if trunk_precision not in ('fp32', 'bf16x3', 'bf16x1'):
+            raise ValueError("trunk_precision must be 'fp32', 'bf16x3' or 'bf16x1', got %r" % (trunk_precision,))
+        self.trunk_precision = trunk_precision    # 'fp32', 'bf16x3' or 'bf16x1': the trunk's routed stride-1 1x1 convs on bf16 pieces (ResnetFeatureExtractor.precision)
         self.upsampler = upsampler                # refiner head: 'compat' (BackwardCompatibleUpsampler, the reference's default) or 'bicubic'
         #                                           (Upsampler, the head of the YouTube-VOS fork); both load the same checkpoint keys
         self.aug_fill = aug_fill                  # first-frame hole fill: 'telea' (the reference's recipe, on the host; default) or 'pull_push' (device-side substitute of rounds 2-5)
@@ -119,9 +119,10 @@ def parse_args(argv=None):
                     help="refiner head: 'compat' (BackwardCompatibleUpsampler, the reference's default) or 'bicubic' (Upsampler, the fork's head)")
     ap.add_argument('--ytvos-fork', action='store_true',
                     help="a checkpoint of the reference's YouTube-VOS fork: shorthand for --ytvos-solver --ytvos-merge --upsampler bicubic")
-    ap.add_argument('--trunk-precision', choices=['fp32', 'bf16x3'], default='fp32',
+    ap.add_argument('--trunk-precision', choices=['fp32', 'bf16x3', 'bf16x1'], default='fp32',
                     help="'bf16x3': the routed stride-1 1x1 trunk convs on three bf16 pieces per operand (not bitwise fp32: 0.78-1.40x the fp32 kernels' max error against fp64; "
-                         "no measurable speed-up of the trunk or the tracker; README, DESIGN.md section 4)")
+                         "no measurable speed-up of the trunk or the tracker); 'bf16x1': on one bf16 piece per operand, fp32 accumulation (NOT fp32-level arithmetic: "
+                         "up to 2^-7 relative error per product); README, DESIGN.md section 4")
     ap.add_argument('--dist-backend', default='nccl', help='nccl (= RCCL); gloo for tests')
     ap.add_argument('--share-gpu', action='store_true', help='tests only: every rank uses cuda:0')
     ap.add_argument('--prewarm', default=None, help='HxW: capture the graphs for this frame size (1-3 objects) before the first sequence')

@@ -115,7 +115,7 @@ class ResNetParams(nn.Module):
         return self
 
 
-_PRECISIONS = {'fp32': 0, 'bf16x3': 1}     # frtm_backbone_set_precision modes
+_PRECISIONS = {'fp32': 0, 'bf16x3': 3, 'bf16x1': 1}     # bf16 pieces per operand (frtm_backbone_set_bf16_pieces)
 
 
 class ResnetFeatureExtractor:
@@ -197,8 +197,9 @@ class ResnetFeatureExtractor:
 
     @property
     def precision(self):
-        """'fp32' (default) or 'bf16x3': the trunk's stride-1 1x1 convs on three bf16 pieces per operand (frtm_backbone_set_precision; the
-        error bound and the routed shapes: DESIGN.md sections 4 and 9).  Every other conv stays fp32."""
+        """'fp32' (default), 'bf16x3' or 'bf16x1': the routed stride-1 1x1 convs of the trunk on three bf16 pieces per operand (fp32-level error), or
+        on one (operands rounded to bf16, fp32 accumulation: NOT fp32-level arithmetic) (frtm_backbone_set_bf16_pieces; the error bounds and the
+        routed shapes: DESIGN.md sections 4 and 9).  Every other conv stays fp32."""
         return self._precision
 
     @precision.setter
@@ -207,7 +208,7 @@ class ResnetFeatureExtractor:
             raise ValueError('precision must be one of %s, got %r' % (sorted(_PRECISIONS), mode))
         if self._handle is not None:
             with torch.cuda.device(self.device):
-                H.call_nostream('frtm_backbone_set_precision', self._handle, _PRECISIONS[mode])      # raises: the mode stays as it was
+                H.call_nostream('frtm_backbone_set_bf16_pieces', self._handle, _PRECISIONS[mode])      # raises: the mode stays as it was
             self._out_cache.clear()           # captured graphs hold the other kernels
         self._precision = mode
 
@@ -280,7 +281,7 @@ class ResnetFeatureExtractor:
                 H.call('frtm_backbone_set_conv', self._handle, i, H.ptr(cv.weight.data.float().contiguous()),
                        H.ptr(scale), H.ptr(shift))
             torch.cuda.current_stream().synchronize()      # the temporaries above die with this scope
-            H.call_nostream('frtm_backbone_set_precision', self._handle, _PRECISIONS[self._precision])
+            H.call_nostream('frtm_backbone_set_bf16_pieces', self._handle, _PRECISIONS[self._precision])
 
     def lane_streams(self):
         """The native trunk's internal streams (lanes 1.. of set 0) as torch streams: a caller that runs other work NEXT TO a pass places

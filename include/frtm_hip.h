@@ -264,7 +264,7 @@ typedef struct {
   int relu, out_transposed;
   int splitk;              /* 0 = auto */
   int tile;                /* 0 = auto, else FRTM_TILE_* */
-  int w_layout;            /* FRTM_WLAYOUT_GEMM (0) or FRTM_WLAYOUT_HALO3X3 (3x3, stride 1 or 2, pad 1 only), ... FRTM_WLAYOUT_BF16X3 (below) */
+  int w_layout;            /* FRTM_WLAYOUT_GEMM (0) or FRTM_WLAYOUT_HALO3X3 (3x3, stride 1 or 2, pad 1 only), ... FRTM_WLAYOUT_BF16X3, FRTM_WLAYOUT_BF16X1 (below) */
   int ws_elems;            /* capacity of `workspace` in floats (0 = no workspace: split-K is disabled); split-K is clamped to it.
                               One workspace must not be used by convolutions that may run concurrently (one per stream). */
   int w_pitch;             /* 0: wT is the padded [Kp][Mp] image of frtm_conv_pack_weights;
@@ -303,6 +303,17 @@ typedef struct {
    to 128, stored in a float buffer of FRTM_CONV_BF16X3_ELEMS floats (16-byte aligned).  Other descriptors return FRTM_ERR_ARG. */
 #define FRTM_WLAYOUT_BF16X3 5
 #define FRTM_CONV_BF16X3_ELEMS(Cout, Cin) ((size_t)3 * (((Cin) + 15) / 16 * 16) * (((Cout) + 127) / 128 * 128) / 2)
+/* bf16x1 (opt-in precision mode, csrc/conv_bf16x1.hip): 1x1, stride 1, pad 0, NCHW output, w_pitch 0, Cin % 16 == 0, splitk 0 or 1; any Cout and H*W.
+   ONE bf16 piece per operand: out = epilogue(sum_k bf16(W) * bf16(X)), operands rounded to nearest even, products on bf16 MFMAs, fp32 accumulation
+   and fp32 epilogue.  NOT fp32-level arithmetic: element-wise |out - exact| <= (2^-7 + 2^-16 + K 2^-22) (|W|.|X|).  NaN stays NaN, Inf stays Inf, |v|
+   above the largest finite bf16 rounds to Inf; denormal operands are whatever the MFMA does with them.  Deterministic, and independent of the tile
+   form and the grid (every output element is one fixed sequence of MFMAs).  `tile`: 0 = automatic (the large form for Cin >= 1024 when it has a tile per
+   CU, else the small one), or FRTM_BF16X1_TILE_128x64 (1), FRTM_BF16X1_TILE_64x64 (2): Cout x pixels.  The image is one bf16 plane [Cin/8][Mp][8], Mp = Cout rounded up to 128, in a float
+   buffer of FRTM_CONV_BF16X1_ELEMS floats (16-byte aligned).  Other descriptors return FRTM_ERR_ARG. */
+#define FRTM_WLAYOUT_BF16X1 6
+#define FRTM_CONV_BF16X1_ELEMS(Cout, Cin) ((size_t)(((Cin) + 15) / 16 * 16) * (((Cout) + 127) / 128 * 128) / 2)
+#define FRTM_BF16X1_TILE_128x64 1
+#define FRTM_BF16X1_TILE_64x64 2
 #define FRTM_WINO_MIN_BLOCKS 512   /* 8x8 output blocks x 32-channel tiles below which callers prefer HALO3X3 + split-K */
 #define FRTM_CONV_PACKED_ELEMS(Cout, Cin, k) \
   (((((Cin) * (k) * (k) + 31) / 32 * 32) > (((Cin) + 7) / 8 * 72) ? (((Cin) * (k) * (k) + 31) / 32 * 32) : (((Cin) + 7) / 8 * 72)) * (((Cout) + 31) / 32 * 32))
@@ -379,6 +390,8 @@ long frtm_conv_persistent_launches(void);
 const char* frtm_conv_last_kernels(void);
 /* Launches of frtm_conv2d (this process) that took the bf16x3 form (FRTM_WLAYOUT_BF16X3, csrc/conv_bf16x3.hip). */
 long frtm_conv_bf16x3_launches(void);
+/* ... and that took the bf16x1 form (FRTM_WLAYOUT_BF16X1, csrc/conv_bf16x1.hip).  The two counters are disjoint. */
+long frtm_conv_bf16x1_launches(void);
 /* Host-side check of the multiplication the conv kernels use instead of integer divisions in their index arithmetic (csrc/conv_common.h: FastDiv,
  * q = (mulhi(n, m) + n) >> s with m, s prepared per divisor): returns n / d as that formula computes it, for 0 <= n < 2^31, d >= 1.
  * No GPU involved; tests/test_cpu_host.py sweeps it against Python's integer division. */
@@ -411,6 +424,13 @@ int frtm_backbone_set_winograd4(frtm_backbone_t* bb, int enable);
  * in both lane sets and every lane; a per-conv plan (frtm_backbone_set_conv_plan) keeps its conv on the fp32 path.  The split weight images are
  * packed when mode 1 is first set (and again by a later frtm_backbone_set_conv); mode 0 allocates nothing.  Bumps the generation. */
 int frtm_backbone_set_precision(frtm_backbone_t* bb, int mode);
+/* The same switch by the number of bf16 pieces per operand: 0 = fp32, 3 = bf16x3 (identical to frtm_backbone_set_precision(bb, 1)), 1 = bf16x1 --
+ * the stride-1 1x1 convs that the bf16x1 router picks (csrc/backbone.hip: bf16x1_route, profiles/bf16x1_trunk_time.txt) run as FRTM_WLAYOUT_BF16X1.
+ * Anything else (2 included) is FRTM_ERR_ARG and leaves the mode as it was.  The two bf16 modes are exclusive: a bf16x1 trunk never launches the
+ * bf16x3 kernel.  Images are packed when the mode is first set (and again by a later frtm_backbone_set_conv); bumps the generation when the mode
+ * changes.  A per-conv plan keeps its conv on the fp32 path.  Environment FRTM_BF16X1_MIN_COLS=n (read at frtm_backbone_create; for tests and
+ * measurements on small frames): every eligible conv of a bf16x1 trunk is routed from n columns per launch on, instead of the measured table. */
+int frtm_backbone_set_bf16_pieces(frtm_backbone_t* bb, int pieces);
 
 /* ------------------------------------------------------------------------------------------
  * Tracker.track mask merge (model/tracker.py:214-221), in place on masks (n_obj+1, H*W).
