@@ -115,6 +115,7 @@ SIGNATURES = {
     'frtm_add_plane': (I, [P, P, F, I, I, P]),
     'frtm_shift9': (I, [P, I, I, I, P, P]),
     'frtm_cab_gate': (I, [P, P, I, P, P, P, P, I, I, P, P]),
+    'frtm_project_tail_fits': (I, [I, I, I, I, I]),
     'frtm_project_tail': (I, [P, I, I, I, I, P, P, I, I, P, P]),
     'frtm_tap_mix': (I, [P, I, I, I, P, P, P]),
     'frtm_bicubic_resize': (I, [P, I, I, I, P, I, I, P]),

@@ -3,22 +3,14 @@
 // them -- bilinear / bicubic resampling, the score-channel injection of TSE, the channel-attention combine -- is HBM-bound
 // element-wise work, one kernel each instead of 5-10 framework launches.
 #include "frtm_common.h"
+#include "resample_taps.h"
 #include "../../include/frtm_hip.h"
 
-// ATen bilinear source taps, align_corners=False (same as target_model.hip)
-__device__ __forceinline__ void bl_taps(int d, float scale, int n_in, int& i0, int& i1, float& l0, float& l1) {
-  float src = __fsub_rn(__fmul_rn(scale, (float)d + 0.5f), 0.5f);
-  src = src < 0.f ? 0.f : src;
-  i0 = (int)src;
-  i1 = i0 + (i0 < n_in - 1 ? 1 : 0);
-  l1 = src - (float)i0;
-  l0 = 1.f - l1;
-}
 __device__ __forceinline__ float bilinear_at(const float* __restrict__ p, int h, int w, int H, int W, int y, int x) {
   if (h == H && w == W) return p[y * w + x];
   int y0, y1, x0, x1; float ly0, ly1, lx0, lx1;
-  bl_taps(y, (float)h / (float)H, h, y0, y1, ly0, ly1);
-  bl_taps(x, (float)w / (float)W, w, x0, x1, lx0, lx1);
+  bilinear_taps(y, (float)h / (float)H, h, y0, y1, ly0, ly1);
+  bilinear_taps(x, (float)w / (float)W, w, x0, x1, lx0, lx1);
   return ly0 * (lx0 * p[y0 * w + x0] + lx1 * p[y0 * w + x1]) + ly1 * (lx0 * p[y1 * w + x0] + lx1 * p[y1 * w + x1]);
 }
 
@@ -30,8 +22,8 @@ __global__ __launch_bounds__(256) void k_bilinear_resize(const float* __restrict
   if (pix >= H * W) return;
   const int y = pix / W, x = pix - y * W;
   int y0, y1, x0, x1; float ly0, ly1, lx0, lx1;
-  bl_taps(y, (float)h / (float)H, h, y0, y1, ly0, ly1);
-  bl_taps(x, (float)w / (float)W, w, x0, x1, lx0, lx1);
+  bilinear_taps(y, (float)h / (float)H, h, y0, y1, ly0, ly1);
+  bilinear_taps(x, (float)w / (float)W, w, x0, x1, lx0, lx1);
   const float w00 = ly0 * lx0, w01 = ly0 * lx1, w10 = ly1 * lx0, w11 = ly1 * lx1;
   const int o00 = y0 * w + x0, o01 = y0 * w + x1, o10 = y1 * w + x0, o11 = y1 * w + x1;
   const int p0 = blockIdx.y * planes_per_z, p1 = min(planes, p0 + planes_per_z);
@@ -102,7 +94,7 @@ __global__ __launch_bounds__(256) void k_cab_combine(const float* __restrict__ s
   const int r0 = blockIdx.x * CAB_RB;
   for (int x = tx; x < W; x += 64) {
     int x0, x1; float lx0, lx1;
-    bl_taps(x, (float)wd / (float)W, wd, x0, x1, lx0, lx1);
+    bilinear_taps(x, (float)wd / (float)W, wd, x0, x1, lx0, lx1);
     float sv[CAB_RB / 4], dv[CAB_RB / 4];
 #pragma unroll
     for (int k = 0; k < CAB_RB / 4; ++k) {                  // all loads of the thread's four rows first (independent), then the stores
@@ -111,7 +103,7 @@ __global__ __launch_bounds__(256) void k_cab_combine(const float* __restrict__ s
         dv[k] = dp[y * wd + x];
       } else {
         int y0, y1; float ly0, ly1;
-        bl_taps(y, (float)hd / (float)H, hd, y0, y1, ly0, ly1);
+        bilinear_taps(y, (float)hd / (float)H, hd, y0, y1, ly0, ly1);
         dv[k] = ly0 * (lx0 * dp[y0 * wd + x0] + lx1 * dp[y0 * wd + x1]) + ly1 * (lx0 * dp[y1 * wd + x0] + lx1 * dp[y1 * wd + x1]);
       }
       sv[k] = sp[y * W + x];
@@ -168,14 +160,13 @@ __global__ __launch_bounds__(256) void k_cab_gate(const float* __restrict__ sp, 
 }
 
 // 2x polyphase bicubic up-sampling, replicate border (seg_network.py:75-126): out = crop1(interleave(conv4x4(pad2(in)))).
-// The taps are the a = -0.75 cubic kernel at d = -0.25 (even phase) / d = -0.75 (odd phase):
-//   even: cubic(1.25), cubic(.25), cubic(.75), cubic(1.75) = -27/256, 225/256, 67/256, -9/256 ; odd: the reverse.
+// The taps are the a = -0.75 cubic kernel at d = -0.25 (even phase: PYR2X_E0 .. E3 of resample_taps.h) / d = -0.75 (odd phase: the reverse).
 // One thread produces a COLUMN STRIP of PYR_Q vertically adjacent 2x2 output quads from the (PYR_Q + 4) x 5 input patch they share: 10 loads per
 // quad instead of 25 and the index arithmetic once per strip (the quad-per-thread form was bound by its loads: 103 us for 64 planes x 10 samples
 // of 120 x 214).  Same expressions per output as before (and as k_project_tail): results unchanged.
 #define PYR_Q 4
 __global__ __launch_bounds__(256) void k_pyrup2x(const float* __restrict__ in, int h, int w, float* __restrict__ out, size_t strips) {
-  const float E[4] = {-0.10546875f, 0.87890625f, 0.26171875f, -0.03515625f};
+  const float E[4] = {PYR2X_E0, PYR2X_E1, PYR2X_E2, PYR2X_E3};
   const int H = 2 * h, W = 2 * w;
   const int G = (h + PYR_Q - 1) / PYR_Q;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < strips; i += (size_t)gridDim.x * 256) {
@@ -250,7 +241,7 @@ __global__ __launch_bounds__(256) void k_plane_mean(const float* __restrict__ in
 #define PT_CG 2
 
 __device__ __forceinline__ float pyr_taps(int odd, float a, float b, float c, float d) {
-  const float E0 = -0.10546875f, E1 = 0.87890625f, E2 = 0.26171875f, E3 = -0.03515625f;
+  const float E0 = PYR2X_E0, E1 = PYR2X_E1, E2 = PYR2X_E2, E3 = PYR2X_E3;
   return odd ? E0 * a + E1 * b + E2 * c + E3 * d : E3 * a + E2 * b + E1 * c + E0 * d;
 }
 
@@ -274,13 +265,13 @@ __global__ __launch_bounds__(256, 4) void k_project_tail(const float* __restrict
   if (tid < PT_ZR) {
     const int zy = Y0 - 1 + tid;
     int i0 = -1, i1 = -1; float l0 = 0.f, l1 = 0.f;
-    if (zy >= 0 && zy < Ho) bl_taps(zy, (float)Hu / (float)Ho, Hu, i0, i1, l0, l1);
+    if (zy >= 0 && zy < Ho) bilinear_taps(zy, (float)Hu / (float)Ho, Hu, i0, i1, l0, l1);
     ri0[tid] = i0; ri1[tid] = i1; rl0[tid] = l0; rl1[tid] = l1;
   }
   if (tid >= 64 && tid < 64 + PT_ZC) {
     const int j = tid - 64, zx = X0 - 1 + j;
     int i0 = -1, i1 = -1; float l0 = 0.f, l1 = 0.f;
-    if (zx >= 0 && zx < Wo) bl_taps(zx, (float)Wu / (float)Wo, Wu, i0, i1, l0, l1);
+    if (zx >= 0 && zx < Wo) bilinear_taps(zx, (float)Wu / (float)Wo, Wu, i0, i1, l0, l1);
     cj0[j] = i0; cj1[j] = i1; cl0[j] = l0; cl1[j] = l1;
   }
   __syncthreads();
@@ -680,14 +671,28 @@ int frtm_pyrup2x(const float* in, int planes, int h, int w, float* out, frtm_str
   return FRTM_OK;
 }
 
+// Whether the fused tail takes a (h,w) -> (Ho,Wo) resize of the map handed to it: the LDS patch of a 16x64 output tile (+1 conv halo) bounds
+// the ratio.  Host only; the one definition of the rule (the argument checks below, ops.project_tail_fits).
+int frtm_project_tail_fits(int bicubic, int h, int w, int Ho, int Wo) {
+  if (h <= 0 || w <= 0 || Ho <= 0 || Wo <= 0) return 0;
+  if (bicubic) {
+    // the source rows / columns an 18 x 66 z patch reads through the cubic taps (one row / column of margin for the rounding of the
+    // source coordinates)
+    const double sy = (double)h / Ho, sx = (double)w / Wo;
+    return (int)((BT_ZR - 1) * sy) + 6 <= BT_YR && (int)((BT_ZC - 1) * sx) + 6 <= BT_YC;
+  }
+  // the rows / columns of the 2x-upsampled map that the patch reads through the bilinear taps
+  const double sy = 2.0 * h / Ho, sx = 2.0 * w / Wo;
+  return (int)(PT_ZR * sy) + 3 <= PT_UR && (int)(PT_ZC * sx) + 3 <= PT_UC;
+}
+
 int frtm_project_tail(const float* y, int n, int C, int h, int w, const float* w3x3, const float* bias, int Ho, int Wo, float* out,
                       frtm_stream_t stream) {
   FRTM_CHECK_ARG(y && w3x3 && out && n > 0 && C > 0 && h > 1 && w > 1 && Ho > 0 && Wo > 0, "frtm_project_tail: bad argument");
   FRTM_CHECK_ARG(n <= 65535, "frtm_project_tail: at most 65535 samples per call (got %d)", n);
-  // LDS patch bounds: the rows / columns of the 2x-upsampled map a 16x64 output tile (+1 halo) reads through the bilinear taps
-  const double sy = 2.0 * h / Ho, sx = 2.0 * w / Wo;
-  FRTM_CHECK_ARG((int)(PT_ZR * sy) + 3 <= PT_UR && (int)(PT_ZC * sx) + 3 <= PT_UC,
-                 "frtm_project_tail: resize ratio %.3f x %.3f outside the fused kernel's patch (use pyrup2x + bilinear_resize + filter_scores)", sy, sx);
+  FRTM_CHECK_ARG(frtm_project_tail_fits(0, h, w, Ho, Wo),
+                 "frtm_project_tail: resize ratio %.3f x %.3f outside the fused kernel's patch (use pyrup2x + bilinear_resize + filter_scores)",
+                 2.0 * h / Ho, 2.0 * w / Wo);
   dim3 g(ceil_div(Wo, PT_TW), ceil_div(Ho, PT_TH), n);
   k_project_tail<<<g, 256, 0, (hipStream_t)stream>>>(y, C, h, w, w3x3, bias, out, Ho, Wo);
   FRTM_LAUNCH_CHECK();
@@ -707,12 +712,9 @@ int frtm_bicubic_resize(const float* in, int planes, int h, int w, float* out, i
 int frtm_project_tail_bicubic(const float* y, int n, int C, int h, int w, const float* w3x3, const float* bias, int Ho, int Wo, float* out,
                               frtm_stream_t stream) {
   FRTM_CHECK_ARG(y && w3x3 && out && n > 0 && C > 0 && h > 0 && w > 0 && Ho > 0 && Wo > 0, "frtm_project_tail_bicubic: bad argument");
-  // LDS patch bounds: the source rows / columns an 18 x 66 z patch (16x64 output tile + conv halo) reads through the cubic taps
-  // (one row / column of margin for the rounding of the source coordinates)
-  const double sy = (double)h / Ho, sx = (double)w / Wo;
-  FRTM_CHECK_ARG((int)((BT_ZR - 1) * sy) + 6 <= BT_YR && (int)((BT_ZC - 1) * sx) + 6 <= BT_YC,
+  FRTM_CHECK_ARG(frtm_project_tail_fits(1, h, w, Ho, Wo),
                  "frtm_project_tail_bicubic: resize ratio %.3f x %.3f outside the fused kernel's patch (use bicubic_resize + filter_scores)",
-                 sy, sx);
+                 (double)h / Ho, (double)w / Wo);
   dim3 g(ceil_div(Wo, BT_TW), ceil_div(Ho, BT_TH), n);
   FRTM_CHECK_ARG(n <= 65535, "frtm_project_tail_bicubic: at most 65535 samples per call");
   k_project_tail_bicubic<<<g, 256, 0, (hipStream_t)stream>>>(y, C, h, w, w3x3, bias, out, Ho, Wo);

@@ -11,6 +11,7 @@
 //   k_shift9              the nine zero-filled shifts of the logit gradient (head tail: conv2's taps before the resampling)
 // No kernel here uses atomics: every sum runs in a fixed order, so two identical backward passes give bit-identical gradients.
 #include "frtm_common.h"
+#include "resample_taps.h"
 #include "../../include/frtm_hip.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -240,7 +241,7 @@ __global__ __launch_bounds__(256) void k_relu_bwd(const float* __restrict__ dy, 
 // weight of input i (of n) in output q of k_pyrup2x along one axis: output 2a reads in[a-2 .. a+1] with (E3,E2,E1,E0), output
 // 2a+1 reads in[a-1 .. a+2] with (E0,E1,E2,E3), indices clamped into the map (replicate border)
 __device__ __forceinline__ float pyr_w(int q, int i, int n) {
-  const float E[4] = {-0.10546875f, 0.87890625f, 0.26171875f, -0.03515625f};
+  const float E[4] = {PYR2X_E0, PYR2X_E1, PYR2X_E2, PYR2X_E3};
   const int a = q >> 1, odd = q & 1;
   float w = 0.f;
 #pragma unroll
@@ -264,16 +265,6 @@ __global__ __launch_bounds__(256) void k_pyrup2x_bwd_axis(const float* __restric
   out[e] = s;
 }
 
-// ATen bilinear taps, align_corners=False: the same expressions as bl_taps of refiner_ops.hip
-__device__ __forceinline__ void blt(int d, float scale, int n_in, int& i0, int& i1, float& l0, float& l1) {
-  float src = __fsub_rn(__fmul_rn(scale, (float)d + 0.5f), 0.5f);
-  src = src < 0.f ? 0.f : src;
-  i0 = (int)src;
-  i1 = i0 + (i0 < n_in - 1 ? 1 : 0);
-  l1 = src - (float)i0;
-  l0 = 1.f - l1;
-}
-
 // in: (outer, Lout, inner) gradient of the resized map, out: (outer, Lin, inner).  The outputs that read input i form one range (the
 // taps are monotone in the output index): [first d with i1(d) >= i, last d with i0(d) <= i], found by bisection.
 __global__ __launch_bounds__(256) void k_bilinear_bwd_axis(const float* __restrict__ in, int Lin, int Lout, int inner, size_t total,
@@ -286,15 +277,15 @@ __global__ __launch_bounds__(256) void k_bilinear_bwd_axis(const float* __restri
   const float scale = (float)Lin / (float)Lout;
   int i0, i1; float l0, l1;
   int lo = 0, hi = Lout;                                      // first d with i1(d) >= i
-  while (lo < hi) { const int m = (lo + hi) >> 1; blt(m, scale, Lin, i0, i1, l0, l1); if (i1 >= i) hi = m; else lo = m + 1; }
+  while (lo < hi) { const int m = (lo + hi) >> 1; bilinear_taps(m, scale, Lin, i0, i1, l0, l1); if (i1 >= i) hi = m; else lo = m + 1; }
   const int d0 = lo;
   lo = 0; hi = Lout;                                          // first d with i0(d) > i
-  while (lo < hi) { const int m = (lo + hi) >> 1; blt(m, scale, Lin, i0, i1, l0, l1); if (i0 > i) hi = m; else lo = m + 1; }
+  while (lo < hi) { const int m = (lo + hi) >> 1; bilinear_taps(m, scale, Lin, i0, i1, l0, l1); if (i0 > i) hi = m; else lo = m + 1; }
   const int d1 = lo;
   const float* p = in + o * (size_t)Lout * inner + b;
   float s = 0.f;
   for (int d = d0; d < d1; ++d) {
-    blt(d, scale, Lin, i0, i1, l0, l1);
+    bilinear_taps(d, scale, Lin, i0, i1, l0, l1);
     const float w = (i0 == i ? l0 : 0.f) + (i1 == i ? l1 : 0.f);
     s += w * p[(size_t)d * inner];
   }

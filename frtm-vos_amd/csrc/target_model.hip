@@ -3,6 +3,7 @@
 // rules here are coalesced 64-lane row access, LDS for the shared 30x54 maps, wave-shuffle
 // reductions with a fixed summation order (deterministic, no float atomics).
 #include "frtm_common.h"
+#include "resample_taps.h"
 #include "../../include/frtm_hip.h"
 
 // ------------------------------------------------------------------------------------------
@@ -62,17 +63,8 @@ __global__ __launch_bounds__(256) void k_pixel_weights_map(const void* __restric
 
 // ------------------------------------------------------------------------------------------
 // Low-res normal equations: one wave per feature-grid cell (i,j) gathers the ~32x32 image pixels
-// whose bilinear support touches it.  ATen taps: src=max(scale*(d+.5)-.5,0), i0=(int)src,
-// i1=i0+(i0<n-1), l1=src-i0, l0=1-l1  (upsample_bilinear2d, align_corners=False).
+// whose bilinear support touches it (ATen taps: bilinear_taps of resample_taps.h).
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ void taps(int d, float scale, int n_in, int& i0, int& i1, float& l0, float& l1) {
-  float src = __fsub_rn(__fmul_rn(scale, (float)d + 0.5f), 0.5f);   // no fma contraction: same rounding as ATen's scalar code
-  src = src < 0.f ? 0.f : src;
-  i0 = (int)src;
-  i1 = i0 + (i0 < n_in - 1 ? 1 : 0);
-  l1 = src - (float)i0;
-  l0 = 1.f - l1;
-}
 __device__ __forceinline__ float tap_w(int k, int i0, int i1, float l0, float l1) {
   return (k == i0 ? l0 : 0.f) + (k == i1 ? l1 : 0.f);
 }
@@ -123,7 +115,7 @@ __global__ __launch_bounds__(256) void k_normal_build(const void* __restrict__ l
     const int X = Xb + lane;
     const bool xin = X < X1;
     int xi0, xi1; float xl0, xl1;
-    taps(xin ? X : X0, sx, w, xi0, xi1, xl0, xl1);
+    bilinear_taps(xin ? X : X0, sx, w, xi0, xi1, xl0, xl1);
     const float wxc = xin ? tap_w(cj, xi0, xi1, xl0, xl1) : 0.f;
     const float wx0 = tap_w(cj - 1, xi0, xi1, xl0, xl1), wx2 = tap_w(cj + 1, xi0, xi1, xl0, xl1);
     for (int Yb = Y0; Yb < Y1; Yb += NB) {
@@ -140,7 +132,7 @@ __global__ __launch_bounds__(256) void k_normal_build(const void* __restrict__ l
       for (int r = 0; r < NB; ++r) {
         const int Y = Yb + r;
         int yi0, yi1; float yl0, yl1;
-        taps(min(Y, Y1 - 1), sy, h, yi0, yi1, yl0, yl1);
+        bilinear_taps(min(Y, Y1 - 1), sy, h, yi0, yi1, yl0, yl1);
         const float wyc = Y < Y1 ? tap_w(ci, yi0, yi1, yl0, yl1) : 0.f;
         const float wy0 = tap_w(ci - 1, yi0, yi1, yl0, yl1), wy2 = tap_w(ci + 1, yi0, yi1, yl0, yl1);
         const float lab = lab_[r];

@@ -347,9 +347,7 @@ class DiscriminatorLoss(MinimizationProblem):
         else:
             feats = m.samples
         s = ops.filter_scores(feats, w2, n=N)
-        Hh, Ww = m.labels_size[-2:]
-        up = torch.empty(N, 1, Hh, Ww, device=s.device)
-        H.call('frtm_bilinear_resize', H.ptr(s), N, self.h, self.w, H.ptr(up), Hh, Ww)
+        up = ops.bilinear_resize(s, m.labels_size[-2:])
         wgt = m.pixel_weights[:N] * m.weights[:N].sqrt().view(-1, 1, 1, 1)                 # :43
         res = wgt * (up - m.labels[:N])
         return TensorList([res] + [float(r) * p_ for r, p_ in zip(self.filter_regs, params)])

@@ -17,6 +17,7 @@ from torch import nn
 
 from .. import _hip as H
 from .. import ops
+from .seg_network import BackwardCompatibleUpsampler, Upsampler, cab_level, project_head
 
 
 def _flipT(w):
@@ -42,7 +43,7 @@ class _Runner:
         shift = None if bias is None else bias.detach().float().contiguous()
         scale = None if shift is None else self.ones(cout)
         n, _, hh, ww = x.shape
-        if k == 3 and self.net.use_winograd and n * ((hh + 7) // 8) * ((ww + 7) // 8) * ((cout + 31) // 32) >= 512:   # as SegNetwork._conv
+        if k == 3 and self.net.use_winograd and ops.wino_launch(n, hh, ww, cout):
             wW = ops.pack_weights(w, wino=True)[0]
             return ops.conv2d(x, wW, cout, 3, 1, 1, scale=scale, shift=shift, residual=residual, relu=relu, splitk=1, w_layout=2)
         wT, ktab, lay = ops.pack_weights(w)
@@ -82,23 +83,11 @@ def _rrb_forward(R, m, x):
     return out, s
 
 
-def _cab_gate(cab, sp, dp):
+def _cab_weights(cab):
+    """The gate's two 1x1 convs as ops.cab_gate takes them: the weights transposed to [in][out]."""
     c = cab.convreluconv
-    n, oc = sp.shape
-    gate = torch.empty(n, oc, device=sp.device)
-    # the transposed weights are held in locals until the launch: a temporary freed inside the argument list can hand its block to the next one
-    w1t = c[0].weight.detach().flatten(1).t().contiguous()
-    w2t = c[2].weight.detach().flatten(1).t().contiguous()
-    H.call('frtm_cab_gate', H.ptr(sp), H.ptr(dp), 0, H.ptr(w1t), H.ptr(c[0].bias.detach()), H.ptr(w2t), H.ptr(c[2].bias.detach()), n, oc,
-           H.ptr(gate))
-    return gate
-
-
-def _mean(x):
-    n, c, hh, ww = x.shape
-    out = torch.empty(n, c, device=x.device)
-    H.call('frtm_plane_mean', H.ptr(x), n * c, hh * ww, H.ptr(out))
-    return out
+    return (c[0].weight.detach().flatten(1).t().contiguous(), c[0].bias.detach(), c[2].weight.detach().flatten(1).t().contiguous(),
+            c[2].bias.detach())
 
 
 class _Grads:
@@ -154,7 +143,6 @@ class _RefinerTrain(torch.autograd.Function):
         dev = scores.device
         R = _Runner(net, dev)
         scores = scores.detach().float().contiguous()
-        n = scores.shape[0]
         sv = {}
         for L, ft in zip(levels, feats):
             T = net.TSE[L]
@@ -168,42 +156,19 @@ class _RefinerTrain(torch.autograd.Function):
             t4 = R.conv(t2, T.transform[4].weight, T.transform[4].bias, relu=True)
             r, rs1 = _rrb_forward(R, net.RRB1[L], t4)
             sv[L] = dict(ft=ft, h=h, r0=r0, x65=x65, t0=t0, t2=t2, t4=t4, rrb1=rs1, r=r, hw=tuple(h.shape[-2:]))
-        x, pool0 = None, _mean(sv[levels[0]].pop('h'))
+        x, pool0 = None, ops.plane_mean(sv[levels[0]].pop('h'))
         for L in levels:
             v = sv[L]
-            r = v['r']
-            sp = _mean(r)
-            dp = pool0 if x is None else _mean(x)
-            gate = _cab_gate(net.CAB[L], sp, dp)
-            out = torch.empty_like(r)
-            Hh, Ww = r.shape[-2:]
-            deeper = pool0 if x is None else x
-            hd, wd = (1, 1) if x is None else tuple(x.shape[-2:])
-            H.call('frtm_cab_combine', H.ptr(r), H.ptr(gate), H.ptr(deeper), n, r.shape[1], hd, wd, 0, Hh, Ww, H.ptr(out))
-            v.update(sp=sp, dp=dp, gate=gate, deeper_hw=(hd, wd))
+            sp = ops.plane_mean(v['r'])
+            out, gate, dp = cab_level(v['r'], sp, x, pool0, _cab_weights(net.CAB[L]), 0)       # one object per frame: nothing shared
+            v.update(sp=sp, dp=dp, gate=gate, deeper_hw=(1, 1) if x is None else tuple(x.shape[-2:]))
             x, v['rrb2'] = _rrb_forward(R, net.RRB2[L], out)
         pj = net.project
-        c, hh, ww = x.shape[1:]
-        u1 = torch.empty(n, c, 2 * hh, 2 * ww, device=dev)
-        H.call('frtm_pyrup2x', H.ptr(x), n * c, hh, ww, H.ptr(u1))
+        u1 = ops.pyrup2x(x)
         y = R.conv(u1, pj.conv1.weight, pj.conv1.bias, relu=True)
-        c2 = y.shape[1]
-        Ho, Wo = int(image_size[-2]), int(image_size[-1])
-        w2 = pj.conv2.weight.detach().contiguous()
-        b2 = pj.conv2.bias.detach().contiguous()
-        if int(18 * 4.0 * hh / Ho) + 3 <= 22 and int(66 * 4.0 * ww / Wo) + 3 <= 76:       # the fused tail of SegNetwork._forward_hip
-            ym = torch.empty(n, 9, 2 * hh, 2 * ww, device=dev)
-            H.call('frtm_tap_mix', H.ptr(y), n, c2, 4 * hh * ww, H.ptr(w2), H.ptr(ym))
-            logits = torch.empty(n, 1, Ho, Wo, device=dev)
-            eye9 = torch.eye(9, device=dev)
-            H.call('frtm_project_tail', H.ptr(ym), n, 9, 2 * hh, 2 * ww, H.ptr(eye9), H.ptr(b2), Ho, Wo, H.ptr(logits))
-        else:
-            u2 = torch.empty(n, c2, 4 * hh, 4 * ww, device=dev)
-            H.call('frtm_pyrup2x', H.ptr(y), n * c2, 2 * hh, 2 * ww, H.ptr(u2))
-            z = u2 if (Ho, Wo) == (4 * hh, 4 * ww) else ops.bilinear_resize(u2, (Ho, Wo))
-            logits = b2.view(1, 1, 1, 1).expand(n, 1, Ho, Wo).contiguous()
-            ops.filter_scores(z, w2, out=logits, accumulate=True)
-        ctx.net, ctx.sv, ctx.head = net, sv, dict(u1=u1, y=y, hw=(hh, ww))
+        # always fused and on conv2's nine tap maps where the resize fits: the backward rests on the tap-mix identity either way
+        logits = project_head(y, pj.conv2.weight.detach().contiguous(), pj.conv2.bias.detach().contiguous(), image_size, False, True, True)
+        ctx.net, ctx.sv, ctx.head = net, sv, dict(u1=u1, y=y, hw=tuple(x.shape[-2:]))
         ctx.params = params
         return logits
 
@@ -221,8 +186,7 @@ class _RefinerTrain(torch.autograd.Function):
         u1, y = ctx.head['u1'], ctx.head['y']
         hh, ww = ctx.head['hw']
         # head tail: T_t = Pyr^T(Bil^T(shift_t(dl))) at (2hh, 2ww); dy_c = sum_t w2[c,t] T_t; dW2[c,t] = sum y_c T_t; db2 = sum dl
-        S = torch.empty(n, 9, Ho, Wo, device=dl.device)
-        H.call('frtm_shift9', H.ptr(dl), n, Ho, Wo, H.ptr(S))
+        S = ops.shift9(dl)
         if (Ho, Wo) != (4 * hh, 4 * ww):
             S = ops.bilinear_backward(S, 4 * hh, 4 * ww)
         Tm = ops.pyrup2x_backward(S)
@@ -246,21 +210,14 @@ class _RefinerTrain(torch.autograd.Function):
             v = sv[L]
             dout = _rrb_backward(R, G, net.RRB2[L], v['rrb2'], dx)
             r, gate = v['r'], v['gate']
-            N, C, Hh, Ww = r.shape
-            a = torch.empty(N, C, device=r.device)
-            b = torch.empty(N, C, device=r.device)
-            H.call('frtm_cab_backward_reduce', H.ptr(dout), H.ptr(r), N * C, Hh * Ww, H.ptr(a), H.ptr(b))
+            a, b = ops.cab_backward_reduce(dout, r)
             cr = net.CAB[L].convreluconv
-            dsp = torch.empty(N, C, device=r.device)
-            ddp = torch.empty(N, C, device=r.device)
-            gw = [torch.empty_like(p) if G.want(p) else None for p in (cr[0].weight, cr[0].bias, cr[2].weight, cr[2].bias)]
-            H.call('frtm_cab_gate_backward', H.ptr(v['sp']), H.ptr(v['dp']), H.ptr(gate), H.ptr(a), H.ptr(b) if i == 0 else None,
-                   H.ptr(cr[0].weight.detach()), H.ptr(cr[0].bias.detach()), H.ptr(cr[2].weight.detach()), N, C,
-                   *[H.ptr(g) for g in gw], H.ptr(dsp), H.ptr(ddp))
-            for p, g in zip((cr[0].weight, cr[0].bias, cr[2].weight, cr[2].bias), gw):
+            cp = (cr[0].weight, cr[0].bias, cr[2].weight, cr[2].bias)
+            *gw, dsp, ddp = ops.cab_gate_backward(v['sp'], v['dp'], gate, a, b if i == 0 else None, cr[0].weight.detach(), cr[0].bias.detach(),
+                                                  cr[2].weight.detach(), grads=[G.want(p) for p in cp])
+            for p, g in zip(cp, gw):
                 G.put(p, g)
-            dr = torch.empty_like(dout)
-            H.call('frtm_cab_backward_shallow', H.ptr(dout), H.ptr(gate), H.ptr(dsp), N * C, Hh * Ww, H.ptr(dr))
+            dr = ops.cab_backward_shallow(dout, gate, dsp)
             if i == 0:
                 dpool0 = ddp                     # deepest: the deeper input is pool0 = mean(TSE.reduce(ft)) itself (gate and broadcast)
             else:
@@ -294,7 +251,6 @@ class _RefinerTrain(torch.autograd.Function):
 
 def forward_train(net, scores, features, image_size):
     """See SegNetwork.forward_train."""
-    from .seg_network import Upsampler, BackwardCompatibleUpsampler
     if isinstance(net.project, Upsampler):
         raise NotImplementedError('SegNetwork.forward_train: the bicubic head (Upsampler) has no HIP backward; train it through forward_torch')
     if not isinstance(net.project, BackwardCompatibleUpsampler):

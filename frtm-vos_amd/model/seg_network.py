@@ -369,7 +369,7 @@ class SegNetwork(nn.Module):
     def _conv(self, x, c, residual=None):
         if c.get('wW') is not None and self.use_winograd:
             n, _, hh, ww = x.shape
-            if n * ((hh + 7) // 8) * ((ww + 7) // 8) * ((c['cout'] + 31) // 32) >= 512:     # FRTM_WINO_MIN_BLOCKS
+            if ops.wino_launch(n, hh, ww, c['cout']):
                 return ops.conv2d(x, c['wW'], c['cout'], 3, 1, 1, scale=c['scale'], shift=c['shift'], residual=residual,
                                   relu=c['relu'], splitk=1, w_layout=2)
         return ops.conv2d(x, c['wT'], c['cout'], c['k'], 1, c['k'] // 2, ktab=c['ktab'], scale=c['scale'], shift=c['shift'],
@@ -379,29 +379,18 @@ class SegNetwork(nn.Module):
         a = self._conv(x, r['c1'])
         return self._conv(self._conv(a, r['b0']), r['b1'], residual=a)
 
-    @staticmethod
-    def _mean(x):
-        n, c, hh, ww = x.shape
-        out = torch.empty(n, c, device=x.device)
-        H.call('frtm_plane_mean', H.ptr(x), n * c, hh * ww, H.ptr(out))
-        return out
-
     def _branch(self, L, p, ft, scores, deepest):
         """Everything of one pyramid level that does not need the deeper level's output: TSE (reduce shared by all objects of a
         frame, score channel injected into transform[0]) and RRB1 (reference seg_network.py:168-171) + the CAB's shallow pool.
         ft: (F,fc,H,W) taps of F frames; scores: (F*n,1,h,w), frame-major."""
-        N, _, sh, sw = scores.shape
-        F_, Hh, Ww = ft.shape[0], ft.shape[-2], ft.shape[-1]
-        group = N // F_
+        group = scores.shape[0] // ft.shape[0]
         h = self._conv(self._conv(ft, p['r0']), p['r2'])                       # TSE.reduce, shared by the objects of a frame
-        pool0 = self._mean(h) if deepest else None                             # (F,oc): deeper input of the deepest CAB
+        pool0 = ops.plane_mean(h) if deepest else None                         # (F,oc): deeper input of the deepest CAB
         base = self._conv(h, p['base'])                                        # object-independent part of transform[0]
-        C0 = p['base']['cout']
-        t0 = torch.empty(N, C0, Hh, Ww, device=scores.device)
-        H.call('frtm_tse_inject', H.ptr(base), H.ptr(p['b0']), H.ptr(p['ws']), H.ptr(scores), N, group, C0, sh, sw, Hh, Ww, H.ptr(t0))
+        t0 = ops.tse_inject(base, p['b0'], p['ws'], scores, group)
         t = self._conv(self._conv(t0, p['t2']), p['t4'])
         r = self._rrb_hip(t, p['rrb1'])
-        return r, self._mean(r), pool0, (h, base, t0, t)
+        return r, ops.plane_mean(r), pool0, (h, base, t0, t)
 
     def _forward_hip(self, scores, features, image_size, side_streams=None):
         """side_streams: optional list of torch streams, one entry per pyramid level but the last (entries may repeat).  The
@@ -417,7 +406,6 @@ class SegNetwork(nn.Module):
         if n % frames != 0:
             raise ValueError('scores (%d samples) must hold the same number of objects for each of the %d frames' % (n, frames))
         group = n // frames
-        dev = scores.device
         levels = list(self.ft_channels)
         cur = torch.cuda.current_stream()
         keep, br = [], {}
@@ -450,77 +438,55 @@ class SegNetwork(nn.Module):
                 order(cur, st)
             r, sp, _, tmp = br[L]
             keep.append(tmp)
-            Hh, Ww = r.shape[-2:]
-            dp = pool0 if x is None else self._mean(x)
-            gate = torch.empty(n, r.shape[1], device=dev)
-            H.call('frtm_cab_gate', H.ptr(sp), H.ptr(dp), group if x is None else 0, H.ptr(p['cab_w1']), H.ptr(p['cab_b1']),
-                   H.ptr(p['cab_w2']), H.ptr(p['cab_b2']), n, r.shape[1], H.ptr(gate))
-            out = torch.empty_like(r)
-            if x is None:       # deepest level: the deeper input is the frame's pooled vector, shared by its objects
-                H.call('frtm_cab_combine', H.ptr(r), H.ptr(gate), H.ptr(pool0), n, r.shape[1], 1, 1, group, Hh, Ww, H.ptr(out))
-            else:
-                H.call('frtm_cab_combine', H.ptr(r), H.ptr(gate), H.ptr(x), n, r.shape[1], x.shape[2], x.shape[3], 0, Hh, Ww, H.ptr(out))
+            out, gate, dp = cab_level(r, sp, x, pool0, (p['cab_w1'], p['cab_b1'], p['cab_w2'], p['cab_b2']), group)
             keep.append((x, gate, out, dp))
             x = self._rrb_hip(out, p['rrb2'])
         pj = P['project']
-        if pj['kind'] == 'bicubic':
-            return self._head_bicubic(x, pj, image_size)
-        c, hh, ww = x.shape[1:]
-        u1 = torch.empty(n, c, 2 * hh, 2 * ww, device=dev)
-        H.call('frtm_pyrup2x', H.ptr(x), n * c, hh, ww, H.ptr(u1))
+        # The 2x step of both heads is frtm_pyrup2x: at exactly 2x, bicubic F.interpolate samples at the offsets -0.25 / -0.75 of PyrUpBicubic2d and
+        # clamps its indices like its replicate padding, so the two are one operator (the GPU test holds pyrup2x to frtm_bicubic_resize at 2x within
+        # 1e-6 relative); pyrup2x reads 10 inputs per 2x2 output quad where the general resize reads 16 per output.
+        u1 = ops.pyrup2x(x)
         y = self._conv(u1, pj['c1'])
-        c2 = y.shape[1]
-        Ho, Wo = int(image_size[-2]), int(image_size[-1])
-        if self.fuse_tail and int(18 * 4.0 * hh / Ho) + 3 <= 22 and int(66 * 4.0 * ww / Wo) + 3 <= 76:
-            # up2 + bilinear resize + conv2 in one kernel: the 32-channel full-resolution tensor never exists in HBM
-            out = torch.empty(n, 1, Ho, Wo, device=dev)
-            if self.mix_taps and c2 > 9:
-                # conv2's channel sum first (it commutes with the resampling): nine maps go through up2 + resize instead of c2 = 32
-                ym = torch.empty(n, 9, 2 * hh, 2 * ww, device=dev)
-                H.call('frtm_tap_mix', H.ptr(y), n, c2, 4 * hh * ww, H.ptr(pj['w2']), H.ptr(ym))
-                H.call('frtm_project_tail', H.ptr(ym), n, 9, 2 * hh, 2 * ww, H.ptr(pj['eye9']), H.ptr(pj['b2']), Ho, Wo, H.ptr(out))
-            else:
-                H.call('frtm_project_tail', H.ptr(y), n, c2, 2 * hh, 2 * ww, H.ptr(pj['w2']), H.ptr(pj['b2']), Ho, Wo, H.ptr(out))
-            return out
-        u2 = torch.empty(n, c2, 4 * hh, 4 * ww, device=dev)
-        H.call('frtm_pyrup2x', H.ptr(y), n * c2, 2 * hh, 2 * ww, H.ptr(u2))
-        if (Ho, Wo) != (4 * hh, 4 * ww):
-            z = torch.empty(n, c2, Ho, Wo, device=dev)
-            H.call('frtm_bilinear_resize', H.ptr(u2), n * c2, 4 * hh, 4 * ww, H.ptr(z), Ho, Wo)
-        else:
-            z = u2
-        out = pj['b2'].view(1, 1, 1, 1).expand(n, 1, Ho, Wo).contiguous()
-        return ops.filter_scores(z, pj['w2'], out=out, accumulate=True)
+        return project_head(y, pj['w2'], pj['b2'], image_size, pj['kind'] == 'bicubic', self.fuse_tail, self.mix_taps and y.shape[1] > 9, pj['eye9'])
 
-    def _head_bicubic(self, x, pj, image_size):
-        """Upsampler.forward on the HIP kernels: 2x bicubic -> conv1 + relu -> bicubic resize to the image size -> conv2, the last two
-        fused (frtm_project_tail_bicubic) on conv2's nine tap maps (frtm_tap_mix) when the resize ratio fits the kernel's patch."""
-        n, c, hh, ww = x.shape
-        dev = x.device
-        # The 2x step is frtm_pyrup2x: at exactly 2x, bicubic F.interpolate samples at the offsets -0.25 / -0.75 of PyrUpBicubic2d and clamps its
-        # indices like its replicate padding, so the two are one operator (the GPU test holds pyrup2x to frtm_bicubic_resize at 2x within 1e-6
-        # relative); pyrup2x reads 10 inputs per 2x2 output quad where the general resize reads 16 per output.
-        u1 = torch.empty(n, c, 2 * hh, 2 * ww, device=dev)
-        H.call('frtm_pyrup2x', H.ptr(x), n * c, hh, ww, H.ptr(u1))
-        y = self._conv(u1, pj['c1'])
-        c2, h2, w2 = y.shape[1], 2 * hh, 2 * ww
-        Ho, Wo = int(image_size[-2]), int(image_size[-1])
-        if self.fuse_tail and bicubic_tail_fits(h2, w2, Ho, Wo):
-            out = torch.empty(n, 1, Ho, Wo, device=dev)
-            if self.mix_taps and c2 > 9:
-                ym = torch.empty(n, 9, h2, w2, device=dev)
-                H.call('frtm_tap_mix', H.ptr(y), n, c2, h2 * w2, H.ptr(pj['w2']), H.ptr(ym))
-                H.call('frtm_project_tail_bicubic', H.ptr(ym), n, 9, h2, w2, H.ptr(pj['eye9']), H.ptr(pj['b2']), Ho, Wo, H.ptr(out))
-            else:
-                H.call('frtm_project_tail_bicubic', H.ptr(y), n, c2, h2, w2, H.ptr(pj['w2']), H.ptr(pj['b2']), Ho, Wo, H.ptr(out))
-            return out
-        z = torch.empty(n, c2, Ho, Wo, device=dev)
-        H.call('frtm_bicubic_resize', H.ptr(y), n * c2, h2, w2, H.ptr(z), Ho, Wo)
-        out = pj['b2'].view(1, 1, 1, 1).expand(n, 1, Ho, Wo).contiguous()
-        return ops.filter_scores(z, pj['w2'], out=out, accumulate=True)
+
+def cab_level(r, sp, x, pool0, weights, group):
+    """The CAB of one pyramid level on the HIP kernels, for the inference and the training path: r (n,oc,H,W) the level's RRB1 output, sp
+    its pooled vector, x the deeper level's output (None at the deepest level, whose deeper input is pool0 (n / group,oc), the pooled
+    TSE.reduce map that the ``group`` objects of a frame share; group 0: one row per sample), weights = (w1t, b1, w2t, b2) of
+    ops.cab_gate.  Returns (out, gate, dp): the combined map, the gate before its sigmoid and the deeper pooled vector."""
+    deepest = x is None
+    dp = pool0 if deepest else ops.plane_mean(x)
+    w1t, b1, w2t, b2 = weights
+    gate = ops.cab_gate(sp, dp, w1t, b1, w2t, b2, group if deepest else 0)
+    return ops.cab_combine(r, gate, pool0 if deepest else x, group if deepest else 0), gate, dp
+
+
+def project_head(y, w2, b2, image_size, bicubic, fused, mixed, eye9=None):
+    """Both heads from conv1's output y (n,c2,h,w) = relu(conv1(2x bicubic(x))) to the logits (n,1,Ho,Wo), for the inference and the training path:
+    the resampling -- up2 + bilinear to the image size (BackwardCompatibleUpsampler) or, ``bicubic``, a bicubic resize to it (Upsampler) --
+    then conv2 (w2 (1,c2,3,3), b2 (1)).
+    ``fused``: resampling + conv2 as one kernel (ops.project_tail) when the resize ratio fits its patch (ops.project_tail_fits), so that the
+    c2-channel full-resolution tensor never exists in HBM; ``mixed``: on conv2's nine tap maps (ops.tap_mix: the channel sum commutes with the
+    resampling, so nine maps are resampled instead of c2 = 32) with the one-hot weights ``eye9`` (made here when None).
+    Otherwise the resampling kernels one by one and an accumulating filter_scores on the bias."""
+    n, _, h, w = y.shape
+    size = (int(image_size[-2]), int(image_size[-1]))
+    if fused and ops.project_tail_fits(h, w, size, bicubic):
+        if mixed:
+            ym = ops.tap_mix(y, w2)
+            return ops.project_tail(ym, torch.eye(9, device=y.device) if eye9 is None else eye9, b2, size, bicubic)
+        return ops.project_tail(y, w2, b2, size, bicubic)
+    if bicubic:
+        z = ops.bicubic_resize(y, size)
+    else:
+        u2 = ops.pyrup2x(y)
+        z = u2 if size == (2 * h, 2 * w) else ops.bilinear_resize(u2, size)
+    out = b2.view(1, 1, 1, 1).expand(n, 1, *size).contiguous()
+    return ops.filter_scores(z, w2, out=out, accumulate=True)
 
 
 def bicubic_tail_fits(h, w, Ho, Wo):
-    """Whether frtm_project_tail_bicubic takes a (h,w) -> (Ho,Wo) resize: the argument check of csrc/refiner_ops.hip (its 18 x 66 z patch
-    reads at most BT_YR = 16 source rows and BT_YC = 40 source columns), evaluated the same way."""
-    return int(17 * (h / Ho)) + 6 <= 16 and int(65 * (w / Wo)) + 6 <= 40
+    """Whether frtm_project_tail_bicubic takes a (h,w) -> (Ho,Wo) resize (its 18 x 66 z patch reads at most BT_YR = 16 source rows and
+    BT_YC = 40 source columns): the library's own argument check."""
+    return ops.project_tail_fits(h, w, (Ho, Wo), bicubic=True)

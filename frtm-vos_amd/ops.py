@@ -1,6 +1,7 @@
 """Thin tensor-level wrappers over the C ABI (include/frtm_hip.h).  Every function enqueues HIP
 kernels on the current torch stream and returns torch tensors that own the device memory."""
 import ctypes
+import functools
 
 import torch
 
@@ -172,6 +173,153 @@ def track_merge(logits, frames, n_obj, masks, labels=None, lut=None, single_obje
 
 
 # ----------------------------------------------------------------------------------------------------------------------
+# Refiner glue (csrc/refiner_ops.hip; model/seg_network.py, model/refiner_train.py)
+#
+# One wrapper per entry point.  Every integer the C side takes is derived from the tensor shapes here, and what it cannot see (ranks,
+# matching batch and channel counts, groups, dtype) is checked first and raises ValueError / TypeError: the library takes pointers, so a
+# transposed h, w pair there is an out-of-bounds access, not an error message.  Weights arrive in the kernel's layout as tensors the caller
+# holds; nothing but the result is allocated and nothing synchronises (safe under graph capture).  A single-frame window is bound by the
+# host, so each check is one condition on the way through and the explanation (_refuse) is worked out only once it has failed.
+# ----------------------------------------------------------------------------------------------------------------------
+WINO_MIN_BLOCKS = 512        # FRTM_WINO_MIN_BLOCKS of include/frtm_hip.h
+
+
+def wino_launch(n, h, w, cout):
+    """The Winograd launch rule of the refiner's 3x3 convs (the trunk's: csrc/backbone.hip): F(2x2,3x3) when the launch has at least
+    FRTM_WINO_MIN_BLOCKS 8x8 output blocks x 32-channel tiles, below that the halo layout with split-K."""
+    return n * ((h + 7) // 8) * ((w + 7) // 8) * ((cout + 31) // 32) >= WINO_MIN_BLOCKS
+
+
+def _refuse(fn, why, **tensors):
+    """The slow path of a wrapper's argument check (the fast one is a single condition): TypeError for the first argument that is not a
+    float32 tensor, else ValueError with what was expected and every shape."""
+    for name, t in tensors.items():
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.float32):
+            raise TypeError('%s: %s must be a float32 tensor, got %s' % (fn, name, t.dtype if isinstance(t, torch.Tensor) else type(t).__name__))
+    raise ValueError('%s: %s; got %s' % (fn, why, ', '.join('%s %s' % (k, tuple(t.shape)) for k, t in tensors.items() if t is not None)))
+
+
+_F32 = torch.float32
+
+
+def plane_mean(x):
+    """adaptive_avg_pool2d(x, 1) of x (N,C,H,W) -> (N,C)."""
+    s = x.shape
+    if len(s) != 4 or x.dtype is not _F32:
+        _refuse('plane_mean', 'x must be (N,C,H,W)', x=x)
+    out = torch.empty(s[0], s[1], device=x.device)
+    H.call('frtm_plane_mean', H.ptr(x), s[0] * s[1], s[2] * s[3], H.ptr(out))
+    return out
+
+
+def pyrup2x(x):
+    """PyrUpBicubic2d: (N,C,h,w) -> (N,C,2h,2w)."""
+    s = x.shape
+    if len(s) != 4 or x.dtype is not _F32:
+        _refuse('pyrup2x', 'x must be (N,C,h,w)', x=x)
+    n, c, h, w = s
+    out = torch.empty(n, c, 2 * h, 2 * w, device=x.device)
+    H.call('frtm_pyrup2x', H.ptr(x), n * c, h, w, H.ptr(out))
+    return out
+
+
+def bicubic_resize(x, size):
+    """F.interpolate(x, size, mode='bicubic', align_corners=False) of x (N,C,h,w)."""
+    s = x.shape
+    Ho, Wo = int(size[-2]), int(size[-1])
+    if len(s) != 4 or Ho < 1 or Wo < 1 or x.dtype is not _F32:
+        _refuse('bicubic_resize', 'x must be (N,C,h,w) and the size %s positive' % ((Ho, Wo),), x=x)
+    n, c, h, w = s
+    out = torch.empty(n, c, Ho, Wo, device=x.device)
+    H.call('frtm_bicubic_resize', H.ptr(x), n * c, h, w, H.ptr(out), Ho, Wo)
+    return out
+
+
+def tse_inject(base, bias, ws, scores, group):
+    """relu(base[s // group] + bias + conv3x3(bilinear(scores[s]), ws)): base (F,C,H,W) the object-independent part of TSE.transform[0],
+    bias (C), ws (C,9) its score-channel taps, scores (F * group,1,h,w) frame-major -> (F * group,C,H,W)."""
+    bs, ss = base.shape, scores.shape
+    group = int(group)
+    if not (len(bs) == 4 == len(ss) and ss[1] == 1 and group > 0 and ss[0] == bs[0] * group and bias.numel() == bs[1] and ws.numel() == 9 * bs[1]
+            and base.dtype is bias.dtype is ws.dtype is scores.dtype is _F32):
+        _refuse('tse_inject', 'expected base (F,C,H,W), bias (C), ws (C,9) and scores (F * group,1,h,w) with group %d' % group,
+                base=base, bias=bias, ws=ws, scores=scores)
+    n, c = ss[0], bs[1]
+    out = torch.empty(n, c, bs[2], bs[3], device=scores.device)
+    H.call('frtm_tse_inject', H.ptr(base), H.ptr(bias), H.ptr(ws), H.ptr(scores), n, group, c, ss[2], ss[3], bs[2], bs[3], H.ptr(out))
+    return out
+
+
+def cab_gate(sp, dp, w1t, b1, w2t, b2, dp_group=0):
+    """The CAB gate before its sigmoid: W2^T relu(W1^T cat(sp, dp) + b1) + b2.  sp (n,oc) pooled shallower and dp pooled deeper features,
+    (n,oc) or, with dp_group > 0, one row per dp_group consecutive samples; w1t (2oc,oc), w2t (oc,oc): the 1x1 conv weights as [in][out]."""
+    ss, ds = sp.shape, dp.shape
+    g = int(dp_group)
+    if not (len(ss) == 2 == len(ds) and g >= 0 and ds[0] * (g or 1) == ss[0] and ds[1] == ss[1] and ss[1] % 4 == 0
+            and w1t.shape == (2 * ss[1], ss[1]) and w2t.numel() == ss[1] * ss[1] and b1.numel() == ss[1] == b2.numel()
+            and sp.dtype is dp.dtype is w1t.dtype is b1.dtype is w2t.dtype is b2.dtype is _F32):
+        _refuse('cab_gate', 'expected sp (n,oc), dp (n,oc) or (n / dp_group,oc) with dp_group %d, oc a multiple of 4, w1t (2oc,oc) and w2t (oc,oc) '
+                'as [in][out], b1 and b2 (oc)' % g, sp=sp, dp=dp, w1t=w1t, b1=b1, w2t=w2t, b2=b2)
+    n, oc = ss
+    gate = torch.empty(n, oc, device=sp.device)
+    H.call('frtm_cab_gate', H.ptr(sp), H.ptr(dp), g, H.ptr(w1t), H.ptr(b1), H.ptr(w2t), H.ptr(b2), n, oc, H.ptr(gate))
+    return gate
+
+
+def cab_combine(shallow, gate, deeper, deeper_group=0):
+    """shallow * sigmoid(gate) + bilinear(deeper): shallow (n,C,H,W), gate (n,C), deeper (n,C,hd,wd) or a pooled (n,C) vector (hd = wd = 1);
+    with deeper_group > 0, deeper holds one entry per deeper_group consecutive samples."""
+    ss, ds = shallow.shape, deeper.shape
+    g = int(deeper_group)
+    if not (len(ss) == 4 and gate.shape == ss[:2] and len(ds) in (2, 4) and g >= 0 and ds[0] * (g or 1) == ss[0] and ds[1] == ss[1]
+            and shallow.dtype is gate.dtype is deeper.dtype is _F32):
+        _refuse('cab_combine', 'expected shallow (n,C,H,W), gate (n,C) and deeper (n,C,hd,wd) or (n,C), n / deeper_group entries with '
+                'deeper_group %d' % g, shallow=shallow, gate=gate, deeper=deeper)
+    hd, wd = (ds[2], ds[3]) if len(ds) == 4 else (1, 1)
+    out = torch.empty_like(shallow)
+    H.call('frtm_cab_combine', H.ptr(shallow), H.ptr(gate), H.ptr(deeper), ss[0], ss[1], hd, wd, g, ss[2], ss[3], H.ptr(out))
+    return out
+
+
+def tap_mix(y, w2):
+    """conv2's channel sum taken before the resampling: y (n,C,h,w), w2 (1,C,3,3) -> the nine tap maps (n,9,h,w)."""
+    s = y.shape
+    if not (len(s) == 4 and w2.numel() == 9 * s[1] and y.dtype is w2.dtype is _F32):
+        _refuse('tap_mix', 'expected y (n,C,h,w) and w2 (1,C,3,3)', y=y, w2=w2)
+    n, c, h, w = s
+    out = torch.empty(n, 9, h, w, device=y.device)
+    H.call('frtm_tap_mix', H.ptr(y), n, c, h * w, H.ptr(w2), H.ptr(out))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def _tail_fits(bicubic, h, w, Ho, Wo):
+    return bool(H.lib().frtm_project_tail_fits(bicubic, h, w, Ho, Wo))
+
+
+def project_tail_fits(h, w, size, bicubic=False):
+    """Whether project_tail takes a (h,w) map -> ``size``: the library's own argument check (frtm_project_tail_fits; a pure function of five
+    integers, remembered per argument set so that a window's head costs no call into the library)."""
+    return _tail_fits(int(bool(bicubic)), int(h), int(w), int(size[-2]), int(size[-1]))
+
+
+def project_tail(y, w3x3, bias, size, bicubic=False):
+    """The fused tail of a head: conv2(resample(y)) + bias -> (n,1,Ho,Wo) with y (n,C,h,w), w3x3 (1,C,3,3), bias (1) or None; the resampling is
+    up2 + bilinear to ``size`` (frtm_project_tail) or, ``bicubic``, a bicubic resize to it (frtm_project_tail_bicubic).  The resize must
+    satisfy project_tail_fits."""
+    s = y.shape
+    Ho, Wo = int(size[-2]), int(size[-1])
+    if not (len(s) == 4 and Ho > 0 and Wo > 0 and w3x3.numel() == 9 * s[1] and y.dtype is w3x3.dtype is _F32
+            and (bias is None or (bias.numel() == 1 and bias.dtype is _F32))):
+        _refuse('project_tail', 'expected y (n,C,h,w), w3x3 (1,C,3,3), bias (1) or None and a positive size, not %s' % ((Ho, Wo),),
+                y=y, w3x3=w3x3, bias=bias)
+    n, c, h, w = s
+    out = torch.empty(n, 1, Ho, Wo, device=y.device)
+    H.call('frtm_project_tail_bicubic' if bicubic else 'frtm_project_tail', H.ptr(y), n, c, h, w, H.ptr(w3x3), H.ptr(bias), Ho, Wo, H.ptr(out))
+    return out
+
+
+# ----------------------------------------------------------------------------------------------------------------------
 # Refiner training (csrc/refiner_train.hip; model/refiner_train.py)
 # ----------------------------------------------------------------------------------------------------------------------
 def conv_wgrad(dy, x, k, weight=True, bias=True):
@@ -257,6 +405,56 @@ def add_plane_(x, v, scale):
     N, C, Hh, Ww = x.shape
     H.call('frtm_add_plane', H.ptr(x), H.ptr(v), float(scale), N * C, Hh * Ww)
     return x
+
+
+def shift9(dl):
+    """The input gradient of a 3x3 conv's nine taps: dl (n,1,H,W) -> (n,9,H,W), dl shifted by each tap, 0 outside."""
+    s = dl.shape
+    if not (len(s) == 4 and s[1] == 1 and dl.dtype is _F32):
+        _refuse('shift9', 'dl must be (n,1,H,W)', dl=dl)
+    out = torch.empty(s[0], 9, s[2], s[3], device=dl.device)
+    H.call('frtm_shift9', H.ptr(dl), s[0], s[2], s[3], H.ptr(out))
+    return out
+
+
+def cab_backward_reduce(dout, s):
+    """Per plane of dout and the CAB's shallower input s (N,C,H,W): (sum dout * s, sum dout), each (N,C)."""
+    ds = dout.shape
+    if not (len(ds) == 4 and s.shape == ds and dout.dtype is s.dtype is _F32):
+        _refuse('cab_backward_reduce', 'dout and s must be (N,C,H,W), one shape', dout=dout, s=s)
+    a = torch.empty(ds[0], ds[1], device=dout.device)
+    b = torch.empty(ds[0], ds[1], device=dout.device)
+    H.call('frtm_cab_backward_reduce', H.ptr(dout), H.ptr(s), ds[0] * ds[1], ds[2] * ds[3], H.ptr(a), H.ptr(b))
+    return a, b
+
+
+def cab_gate_backward(sp, dp, gate, a, badd, w1, b1, w2, grads=(True, True, True, True)):
+    """Backward of cab_gate and the sigmoid from a = sum dout * s: sp, dp, gate, a (n,oc); badd (n,oc) or None is added to ddp; w1 (oc,2oc,1,1)
+    and w2 (oc,oc,1,1) in the conv layout, b1 (oc).  -> (dW1, db1, dW2, db2, dsp, ddp), the first four shaped like the parameters and None
+    where ``grads`` is false."""
+    ss = sp.shape
+    if not (len(ss) == 2 and dp.shape == ss and gate.shape == ss and a.shape == ss and (badd is None or (badd.shape == ss and badd.dtype is _F32))
+            and w1.numel() == 2 * ss[1] * ss[1] and b1.numel() == ss[1] and w2.numel() == ss[1] * ss[1]
+            and sp.dtype is dp.dtype is gate.dtype is a.dtype is w1.dtype is b1.dtype is w2.dtype is _F32):
+        _refuse('cab_gate_backward', 'expected sp, dp, gate, a and badd (or None) of one shape (n,oc), w1 (oc,2oc,1,1), b1 (oc) and w2 (oc,oc,1,1)',
+                sp=sp, dp=dp, gate=gate, a=a, badd=badd, w1=w1, b1=b1, w2=w2)
+    n, oc = ss
+    dsp = torch.empty(n, oc, device=sp.device)
+    ddp = torch.empty(n, oc, device=sp.device)
+    gw = [torch.empty_like(p) if g else None for p, g in zip((w1, b1, w2, b1), grads)]
+    H.call('frtm_cab_gate_backward', H.ptr(sp), H.ptr(dp), H.ptr(gate), H.ptr(a), H.ptr(badd), H.ptr(w1), H.ptr(b1), H.ptr(w2), n, oc,
+           *[H.ptr(g) for g in gw], H.ptr(dsp), H.ptr(ddp))
+    return (*gw, dsp, ddp)
+
+
+def cab_backward_shallow(dout, gate, dsp):
+    """dout * sigmoid(gate) + dsp / (H * W): the gradient of the CAB's shallower input; dout (N,C,H,W), gate and dsp (N,C)."""
+    ds = dout.shape
+    if not (len(ds) == 4 and gate.shape == ds[:2] and dsp.shape == ds[:2] and dout.dtype is gate.dtype is dsp.dtype is _F32):
+        _refuse('cab_backward_shallow', 'expected dout (N,C,H,W), gate and dsp (N,C)', dout=dout, gate=gate, dsp=dsp)
+    out = torch.empty_like(dout)
+    H.call('frtm_cab_backward_shallow', H.ptr(dout), H.ptr(gate), H.ptr(dsp), ds[0] * ds[1], ds[2] * ds[3], H.ptr(out))
+    return out
 
 
 # ----------------------------------------------------------------------------------------------------------------------

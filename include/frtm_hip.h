@@ -472,6 +472,10 @@ int frtm_cab_gate(const float* sp, const float* dp, int dp_group, const float* W
                   int n, int oc, float* gate, frtm_stream_t stream);
 /* PyrUpBicubic2d: 2x polyphase bicubic with replicate border (seg_network.py:75-126); out (planes,2h,2w) */
 int frtm_pyrup2x(const float* in, int planes, int h, int w, float* out, frtm_stream_t stream);
+/* Whether the fused tail takes a (h,w) -> (Ho,Wo) resize (1) or its LDS patch is too small for the ratio (0).  h, w: the size of the map
+ * handed to the tail kernel; bicubic == 0: frtm_project_tail, else frtm_project_tail_bicubic.  Host only, no launch: the argument
+ * checks of the two entry points call it, and so do their callers to choose between the fused and the unfused form. */
+int frtm_project_tail_fits(int bicubic, int h, int w, int Ho, int Wo);
 /* Tail of BackwardCompatibleUpsampler.forward (model/seg_network.py:117-119) in one kernel:
  *   out[n,0] = conv2(interpolate(up2(y[n]), (Ho,Wo), bilinear, align_corners=False)) + bias
  * y (n,C,h,w) is relu(conv1(up1(x))); up2 = PyrUpBicubic2d (2x), conv2 = 3x3, C -> 1, zero padding.  w3x3 (1,C,3,3), bias (1)

@@ -7,6 +7,8 @@
     counterpart and of tests/test_refiner_train_gpu.py hold the kernel to a float64 definition; k_project_tail, k_bicubic_resize and
     k_project_tail_bicubic map to their existing direct tests, which compare with fp32 PyTorch (and the unfused HIP kernels) under
     scalar gates of 1e-5 to 2e-6.  A kernel added without an entry fails test_every_kernel_is_covered.
+(c) One definition per launch and rule: the two model files name no C entry point, frtm_project_tail_fits is the literal fit rule over
+    every size of either axis, and each ops.py wrapper of a glue kernel refuses, on CPU tensors, what the C side cannot see.
 """
 import ast
 import os
@@ -240,3 +242,142 @@ def test_add_plane_reference_is_the_mean_backward():
     x = x0.clone().requires_grad_()
     auto = torch.autograd.grad(x.mean(1), x, v)[0]
     _close(R.add_plane(x0, v, 1.0 / 35), x0 + auto, 'add_plane')
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# (c) one definition per launch and per rule: the model files launch through ops.py, the fit rule is the library's, and the wrappers refuse
+#     what the C side cannot see
+# ---------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('name', ['seg_network.py', 'refiner_train.py'])
+def test_model_files_launch_through_ops(name):
+    """No C entry point is named in a string literal of the two model files: every glue launch goes through its ops.py wrapper."""
+    src = open(os.path.join(ROOT, 'frtm-vos_amd', 'model', name)).read()
+    assert len(src) > 5000
+    assert re.findall(r'''['"]frtm_\w*''', src) == []
+
+
+def _fit_literal(bicubic, h, w, Ho, Wo):
+    if bicubic:
+        return int(17 * (h / Ho)) + 6 <= 16 and int(65 * (w / Wo)) + 6 <= 40
+    return int(18 * (2.0 * h / Ho)) + 3 <= 22 and int(66 * (2.0 * w / Wo)) + 3 <= 76
+
+
+@pytest.mark.parametrize('axis', ['rows', 'columns'])
+@pytest.mark.parametrize('bicubic', [0, 1])
+def test_project_tail_fits_is_the_literal_rule(bicubic, axis):
+    """frtm_project_tail_fits over every map size 2 ... 800 (even) and output size 1 ... 2400 of one axis, the other axis at a size that fits
+    (rows and columns are independent factors of the rule), and with the other axis at one that does not."""
+    from frtm_vos_amd import _hip as H
+    fits = H.lib().frtm_project_tail_fits
+    assert _fit_literal(bicubic, 2, 2, 4, 4) and not _fit_literal(bicubic, 2, 2, 1, 1)
+    bad = []
+    for a in range(2, 801, 2):
+        for o in range(1, 2401):
+            args = (a, 2, o, 4) if axis == 'rows' else (2, a, 4, o)
+            if bool(fits(bicubic, *args)) != _fit_literal(bicubic, *args):
+                bad.append(args)
+        args = (a, 2, 2 * a, 1) if axis == 'rows' else (2, a, 1, 2 * a)             # this axis fits, the other does not
+        assert _fit_literal(bicubic, a, a, 2 * a, 2 * a) and not fits(bicubic, *args)
+    assert bad == [], bad[:10]
+    if not bicubic:      # the spelling the two model files used before they asked the library (hh = h / 2, the map before conv1's 2x step)
+        k, lim = (18, 22) if axis == 'rows' else (66, 76)
+        assert all((int(k * 4.0 * (a // 2) / o) + 3 <= lim) == (int(k * (2.0 * a / o)) + 3 <= lim) for a in range(2, 801, 2) for o in range(1, 2401))
+    assert not fits(bicubic, 0, 2, 4, 4) and not fits(bicubic, 2, 2, 0, 4)
+
+
+def test_project_tail_fits_wrappers():
+    from frtm_vos_amd import ops
+    from frtm_vos_amd.model.seg_network import bicubic_tail_fits
+    for h, w, Ho, Wo in ((240, 428, 480, 854), (240, 428, 240, 427), (56, 76, 90, 150), (28, 38, 30, 45), (240, 428, 481, 854)):
+        assert ops.project_tail_fits(h, w, (Ho, Wo)) == _fit_literal(0, h, w, Ho, Wo)
+        assert ops.project_tail_fits(h, w, (1, 3, Ho, Wo), bicubic=True) == _fit_literal(1, h, w, Ho, Wo) == bicubic_tail_fits(h, w, Ho, Wo)
+
+
+def test_wino_launch_rule():
+    from frtm_vos_amd import ops
+    assert ops.WINO_MIN_BLOCKS == int(re.search(r'#define FRTM_WINO_MIN_BLOCKS (\d+)', open(os.path.join(ROOT, 'include', 'frtm_hip.h')).read()).group(1))
+    assert ops.wino_launch(4, 120, 214, 64) and not ops.wino_launch(4, 30, 54, 64)
+    assert ops.wino_launch(2, 60, 107, 64) is False and ops.wino_launch(3, 60, 107, 64) is True      # 448 and 672 blocks
+    assert ops.wino_launch(8, 57, 57, 33) and not ops.wino_launch(8, 56, 56, 32)                      # 1024 (rounded up) and 392
+
+
+def _t(*shape, dtype=torch.float32):
+    return torch.zeros(*shape, dtype=dtype)
+
+
+# n = 6 samples in groups of 3, C = 8 channels, maps 5 x 7 -> 9 x 13, image 18 x 26; every call differs from a valid one in one argument
+_N, _G, _C = 6, 3, 8
+_GATE_W = lambda: (_t(2 * _C, _C), _t(_C), _t(_C, _C), _t(_C))
+_GB = lambda **k: dict(dict(sp=_t(_N, _C), dp=_t(_N, _C), gate=_t(_N, _C), a=_t(_N, _C), badd=None, w1=_t(_C, 2 * _C, 1, 1), b1=_t(_C), w2=_t(_C, _C, 1, 1)), **k)
+REFUSALS = [
+    ('plane_mean', lambda o: o.plane_mean(_t(_N, _C, 9)), ValueError),
+    ('plane_mean', lambda o: o.plane_mean(_t(_N, _C, 9, 13, dtype=torch.float64)), TypeError),
+    ('pyrup2x', lambda o: o.pyrup2x(_t(_C, 5, 7)), ValueError),
+    ('pyrup2x', lambda o: o.pyrup2x(_t(_N, _C, 5, 7, dtype=torch.float16)), TypeError),
+    ('bicubic_resize', lambda o: o.bicubic_resize(_t(_N * _C, 5, 7), (9, 13)), ValueError),
+    ('bicubic_resize', lambda o: o.bicubic_resize(_t(_N, _C, 5, 7), (0, 13)), ValueError),
+    ('bicubic_resize', lambda o: o.bicubic_resize(_t(_N, _C, 5, 7).int(), (9, 13)), TypeError),
+    ('tse_inject', lambda o: o.tse_inject(_t(2, _C, 9, 13), _t(_C), _t(_C, 9), _t(_N, 1, 5, 7), 2), ValueError),          # 2 frames x 2 != 6
+    ('tse_inject', lambda o: o.tse_inject(_t(2, _C, 9, 13), _t(_C), _t(_C, 9), _t(_N, 1, 5, 7), 4), ValueError),          # 6 % 4
+    ('tse_inject', lambda o: o.tse_inject(_t(2, _C, 9, 13), _t(_C), _t(_C, 9), _t(_N, 2, 5, 7), _G), ValueError),         # two score channels
+    ('tse_inject', lambda o: o.tse_inject(_t(2, _C, 9, 13), _t(_C), _t(_C, 9), _t(_N, 5, 7), _G), ValueError),            # rank
+    ('tse_inject', lambda o: o.tse_inject(_t(2, _C, 9, 13), _t(_C + 1), _t(_C, 9), _t(_N, 1, 5, 7), _G), ValueError),     # bias channels
+    ('tse_inject', lambda o: o.tse_inject(_t(2, _C, 9, 13), _t(_C), _t(_C, 3), _t(_N, 1, 5, 7), _G), ValueError),         # taps
+    ('tse_inject', lambda o: o.tse_inject(_t(2, _C, 9, 13), _t(_C), _t(_C, 9), _t(_N, 1, 5, 7), 0), ValueError),
+    ('tse_inject', lambda o: o.tse_inject(_t(2, _C, 9, 13), _t(_C), _t(_C, 9).double(), _t(_N, 1, 5, 7), _G), TypeError),
+    ('cab_gate', lambda o: o.cab_gate(_t(_N, _C), _t(_N, _C + 4), *_GATE_W()), ValueError),                               # channels differ
+    ('cab_gate', lambda o: o.cab_gate(_t(_N, _C), _t(3, _C), *_GATE_W(), dp_group=_G), ValueError),                       # 3 rows, 6 / 3 = 2
+    ('cab_gate', lambda o: o.cab_gate(_t(_N, _C), _t(2, _C), *_GATE_W(), dp_group=0), ValueError),
+    ('cab_gate', lambda o: o.cab_gate(_t(_N, _C), _t(_N, _C), *_GATE_W(), dp_group=-1), ValueError),
+    ('cab_gate', lambda o: o.cab_gate(_t(_N, _C), _t(_N, _C), _t(_C, 2 * _C), _t(_C), _t(_C, _C), _t(_C)), ValueError),   # w1 not transposed
+    ('cab_gate', lambda o: o.cab_gate(_t(_N, _C), _t(_N, _C), _t(2 * _C, _C), _t(_C), _t(_C, _C), _t(_C + 1)), ValueError),
+    ('cab_gate', lambda o: o.cab_gate(_t(_N, 6), _t(_N, 6), _t(12, 6), _t(6), _t(6, 6), _t(6)), ValueError),              # oc % 4
+    ('cab_gate', lambda o: o.cab_gate(_t(_N, _C, 1, 1), _t(_N, _C), *_GATE_W()), ValueError),
+    ('cab_gate', lambda o: o.cab_gate(_t(_N, _C), _t(_N, _C).double(), *_GATE_W()), TypeError),
+    ('cab_combine', lambda o: o.cab_combine(_t(_N, _C, 9, 13), _t(_N, _C + 1), _t(_N, _C, 5, 7)), ValueError),
+    ('cab_combine', lambda o: o.cab_combine(_t(_N, _C, 9, 13), _t(_N, _C), _t(_N, _C + 1, 5, 7)), ValueError),
+    ('cab_combine', lambda o: o.cab_combine(_t(_N, _C, 9, 13), _t(_N, _C), _t(2, _C, 5, 7)), ValueError),                 # 2 deeper maps, group 0
+    ('cab_combine', lambda o: o.cab_combine(_t(_N, _C, 9, 13), _t(_N, _C), _t(3, _C), deeper_group=_G), ValueError),      # pooled: 3 rows, 6 / 3 = 2
+    ('cab_combine', lambda o: o.cab_combine(_t(_N, _C, 9, 13), _t(_N, _C), _t(2, _C), deeper_group=4), ValueError),
+    ('cab_combine', lambda o: o.cab_combine(_t(_N, _C, 9, 13), _t(_N, _C), _t(_N, _C, 5)), ValueError),                   # rank 3
+    ('cab_combine', lambda o: o.cab_combine(_t(_N, _C, 9, 13), _t(_N, _C), _t(_N, _C, 5, 7).half()), TypeError),
+    ('tap_mix', lambda o: o.tap_mix(_t(_N, _C, 9, 13), _t(1, _C + 1, 3, 3)), ValueError),
+    ('tap_mix', lambda o: o.tap_mix(_t(_N, _C, 9 * 13), _t(1, _C, 3, 3)), ValueError),
+    ('tap_mix', lambda o: o.tap_mix(_t(_N, _C, 9, 13), _t(1, _C, 3, 3).double()), TypeError),
+    ('project_tail', lambda o: o.project_tail(_t(_N, 9, 9, 13), _t(1, _C, 3, 3), _t(1), (18, 26)), ValueError),             # weights of 8 channels, 9 maps
+    ('project_tail', lambda o: o.project_tail(_t(_N, _C, 9, 13), _t(1, _C, 3, 3), _t(2), (18, 26)), ValueError),
+    ('project_tail', lambda o: o.project_tail(_t(_N, _C, 9, 13), _t(1, _C, 3, 3), None, (18, 0), bicubic=True), ValueError),
+    ('project_tail', lambda o: o.project_tail(_t(_N * _C, 9, 13), _t(1, _C, 3, 3), None, (18, 26)), ValueError),
+    ('project_tail', lambda o: o.project_tail(_t(_N, _C, 9, 13).double(), _t(1, _C, 3, 3), None, (18, 26)), TypeError),
+    ('shift9', lambda o: o.shift9(_t(_N, 2, 18, 26)), ValueError),
+    ('shift9', lambda o: o.shift9(_t(_N, 18, 26)), ValueError),
+    ('shift9', lambda o: o.shift9(_t(_N, 1, 18, 26).double()), TypeError),
+    ('cab_backward_reduce', lambda o: o.cab_backward_reduce(_t(_N, _C, 9, 13), _t(_N, _C, 13, 9)), ValueError),
+    ('cab_backward_reduce', lambda o: o.cab_backward_reduce(_t(_N, _C, 9, 13), _t(_N * _C, 9 * 13)), ValueError),
+    ('cab_backward_reduce', lambda o: o.cab_backward_reduce(_t(_N, _C, 9, 13), _t(_N, _C, 9, 13).double()), TypeError),
+    ('cab_gate_backward', lambda o: o.cab_gate_backward(**_GB(dp=_t(2, _C))), ValueError),
+    ('cab_gate_backward', lambda o: o.cab_gate_backward(**_GB(gate=_t(_C, _N))), ValueError),
+    ('cab_gate_backward', lambda o: o.cab_gate_backward(**_GB(badd=_t(_N, _C, 1))), ValueError),
+    ('cab_gate_backward', lambda o: o.cab_gate_backward(**_GB(w1=_t(_C, _C, 1, 1))), ValueError),
+    ('cab_gate_backward', lambda o: o.cab_gate_backward(**_GB(w2=_t(_C, 2 * _C, 1, 1))), ValueError),
+    ('cab_gate_backward', lambda o: o.cab_gate_backward(**_GB(b1=_t(2 * _C))), ValueError),
+    ('cab_gate_backward', lambda o: o.cab_gate_backward(**_GB(a=_t(_N, _C).double())), TypeError),
+    ('cab_backward_shallow', lambda o: o.cab_backward_shallow(_t(_N, _C, 9, 13), _t(_N, _C + 1), _t(_N, _C)), ValueError),
+    ('cab_backward_shallow', lambda o: o.cab_backward_shallow(_t(_N, _C, 9, 13), _t(_N, _C), _t(_N * _C)), ValueError),
+    ('cab_backward_shallow', lambda o: o.cab_backward_shallow(_t(_N, _C, 9, 13), _t(_N, _C), _t(_N, _C).double()), TypeError),
+]
+
+
+@pytest.mark.parametrize('i', range(len(REFUSALS)), ids=['%s-%d' % (r[0], i) for i, r in enumerate(REFUSALS)])
+def test_wrapper_refuses_before_any_device_check(i):
+    """CPU tensors and no launch: the shape, group and dtype checks come before anything that needs a device, and the message names the wrapper."""
+    from frtm_vos_amd import ops
+    name, call, exc = REFUSALS[i]
+    with pytest.raises(exc, match='^' + name + ': '):
+        call(ops)
+
+
+def test_every_new_wrapper_has_a_refusal_case():
+    assert {r[0] for r in REFUSALS} == {'plane_mean', 'pyrup2x', 'bicubic_resize', 'tse_inject', 'cab_gate', 'cab_combine', 'tap_mix', 'project_tail',
+                                        'shift9', 'cab_backward_reduce', 'cab_gate_backward', 'cab_backward_shallow'}
+    assert all(any(r[0] == n and r[2] is e for r in REFUSALS) for n in {r[0] for r in REFUSALS} for e in (ValueError, TypeError))

@@ -17,7 +17,9 @@ which changes the exponential by a relative 0.37 * |g| * 2^-24 at most; the hard
 Output hygiene: every output buffer is pre-filled with NaN and sits between two guard bands of 64 floats, which must stay untouched;
 an output that still holds a NaN was not written.
 
-No test here asserts a time.  The module (314 tests) ran in 117 s on an MI355X in a fresh account (MIOpen choosing kernels for
+The ops.py wrappers of these entry points are held, bit for bit, to the direct call with hand-written dimensions (last section).
+
+No test here asserts a time.  The module (314 tests before the wrapper cases) ran in 117 s on an MI355X in a fresh account (MIOpen choosing kernels for
 the fp32 torch legs, the float64 legs on the CPU) and in 9 s with MIOpen's choices cached.
 """
 import math
@@ -449,3 +451,91 @@ def test_cab_combine_refuses_empty_maps_and_ragged_groups():
         _call('frtm_cab_combine', _z(1, 1, 1, 1), _z(1, 1), _z(1, 1, 1, 1), 1, 1, 0, 1, 0, 1, 1, _z(1, 1, 1, 1))
     with pytest.raises(RuntimeError, match='frtm_cab_combine: 3 samples are not a multiple of deeper_group 2'):
         _call('frtm_cab_combine', _z(3, 1, 1, 1), _z(3, 1), _z(2, 1, 1, 1), 3, 1, 1, 1, 2, 1, 1, _z(3, 1, 1, 1))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the ops.py wrappers: each derives the integers of its launch from the tensor shapes; here every one is held, bit for bit, to the direct
+# call with the dimensions written out by hand.  No two dimensions coincide (n = 6 in groups of 3, C = 8, maps 5 x 7 -> 9 x 13, image
+# 18 x 26), so a transposed pair shows.
+# ---------------------------------------------------------------------------------------------------------------------------------
+def _wrapper_case(name):
+    from frtm_vos_amd import ops
+    g = _gen(*name.encode())
+    d = lambda *shape: _randn(g, *shape).to(DEV)
+    n, grp, C, h, w, Hh, Ww, Ho, Wo = 6, 3, 8, 5, 7, 9, 13, 18, 26
+    if name == 'plane_mean':
+        x, o = d(n, C, Hh, Ww), _Out(n, C)
+        _call('frtm_plane_mean', x, 48, 117, o.t)
+        return ops.plane_mean(x), o
+    if name == 'pyrup2x':
+        x, o = d(n, C, h, w), _Out(n, C, 10, 14)
+        _call('frtm_pyrup2x', x, 48, 5, 7, o.t)
+        return ops.pyrup2x(x), o
+    if name == 'bicubic_resize':
+        x, o = d(n, C, h, w), _Out(n, C, Hh, Ww)
+        _call('frtm_bicubic_resize', x, 48, 5, 7, o.t, 9, 13)
+        return ops.bicubic_resize(x, (Hh, Ww)), o
+    if name == 'tse_inject':
+        base, bias, ws, scores, o = d(2, C, Hh, Ww), d(C), d(C, 9), d(n, 1, h, w), _Out(n, C, Hh, Ww)
+        _call('frtm_tse_inject', base, bias, ws, scores, 6, 3, 8, 5, 7, 9, 13, o.t)
+        return ops.tse_inject(base, bias, ws, scores, grp), o
+    if name in ('cab_gate', 'cab_gate_shared'):
+        shared = name == 'cab_gate_shared'
+        sp, dp, W1, b1, W2, b2, o = d(n, C), d(2 if shared else n, C), d(2 * C, C), d(C), d(C, C), d(C), _Out(n, C)
+        _call('frtm_cab_gate', sp, dp, 3 if shared else 0, W1, b1, W2, b2, 6, 8, o.t)
+        return ops.cab_gate(sp, dp, W1, b1, W2, b2, dp_group=grp if shared else 0), o
+    if name == 'cab_combine':
+        shallow, gate, deeper, o = d(n, C, Hh, Ww), d(n, C), d(n, C, h, w), _Out(n, C, Hh, Ww)
+        _call('frtm_cab_combine', shallow, gate, deeper, 6, 8, 5, 7, 0, 9, 13, o.t)
+        return ops.cab_combine(shallow, gate, deeper), o
+    if name == 'cab_combine_pooled':
+        shallow, gate, pooled, o = d(n, C, Hh, Ww), d(n, C), d(2, C), _Out(n, C, Hh, Ww)
+        _call('frtm_cab_combine', shallow, gate, pooled, 6, 8, 1, 1, 3, 9, 13, o.t)
+        return ops.cab_combine(shallow, gate, pooled, deeper_group=grp), o
+    if name == 'tap_mix':
+        y, w2, o = d(n, C, Hh, Ww), d(1, C, 3, 3), _Out(n, 9, Hh, Ww)
+        _call('frtm_tap_mix', y, 6, 8, 117, w2, o.t)
+        return ops.tap_mix(y, w2), o
+    if name in ('project_tail', 'project_tail_bicubic', 'project_tail_no_bias'):
+        y, w2, o = d(n, C, Hh, Ww), d(1, C, 3, 3), _Out(n, 1, Ho, Wo)
+        bias = None if name == 'project_tail_no_bias' else d(1)
+        assert ops.project_tail_fits(Hh, Ww, (Ho, Wo), name == 'project_tail_bicubic')
+        _call('frtm_' + name.replace('_no_bias', ''), y, 6, 8, 9, 13, w2, bias, 18, 26, o.t)
+        return ops.project_tail(y, w2, bias, (Ho, Wo), bicubic=name == 'project_tail_bicubic'), o
+    if name == 'shift9':
+        dl, o = d(n, 1, Ho, Wo), _Out(n, 9, Ho, Wo)
+        _call('frtm_shift9', dl, 6, 18, 26, o.t)
+        return ops.shift9(dl), o
+    if name == 'cab_backward_reduce':
+        dout, s, a, b = d(n, C, Hh, Ww), d(n, C, Hh, Ww), _Out(n, C), _Out(n, C)
+        _call('frtm_cab_backward_reduce', dout, s, 48, 117, a.t, b.t)
+        return ops.cab_backward_reduce(dout, s), (a, b)
+    if name in ('cab_gate_backward', 'cab_gate_backward_frozen'):
+        frozen = name.endswith('frozen')
+        sp, dp, gate, a, W1, b1, W2 = d(n, C), d(n, C), d(n, C), d(n, C), d(C, 2 * C, 1, 1), d(C), d(C, C, 1, 1)
+        badd = None if frozen else d(n, C)
+        outs = [None] * 4 if frozen else [_Out(C, 2 * C, 1, 1), _Out(C), _Out(C, C, 1, 1), _Out(C)]
+        outs += [_Out(n, C), _Out(n, C)]
+        _call('frtm_cab_gate_backward', sp, dp, gate, a, badd, W1, b1, W2, 6, 8, *[o if o is None else o.t for o in outs])
+        return ops.cab_gate_backward(sp, dp, gate, a, badd, W1, b1, W2, grads=(not frozen,) * 4), outs
+    if name == 'cab_backward_shallow':
+        dout, gate, dsp, o = d(n, C, Hh, Ww), d(n, C), d(n, C), _Out(n, C, Hh, Ww)
+        _call('frtm_cab_backward_shallow', dout, gate, dsp, 48, 117, o.t)
+        return ops.cab_backward_shallow(dout, gate, dsp), o
+    raise KeyError(name)
+
+
+@pytest.mark.parametrize('name', ['plane_mean', 'pyrup2x', 'bicubic_resize', 'tse_inject', 'cab_gate', 'cab_gate_shared', 'cab_combine', 'cab_combine_pooled',
+                                  'tap_mix', 'project_tail', 'project_tail_bicubic', 'project_tail_no_bias', 'shift9', 'cab_backward_reduce',
+                                  'cab_gate_backward', 'cab_gate_backward_frozen', 'cab_backward_shallow'])
+def test_wrapper_equals_the_direct_call(name):
+    got, want = _wrapper_case(name)
+    got, want = (got, want) if isinstance(got, tuple) else ((got,), (want,))
+    assert len(got) == len(want)
+    for a, o in zip(got, want):
+        if o is None:
+            assert a is None
+            continue
+        b = o.done()
+        assert a.shape == b.shape and a.dtype == b.dtype and a.is_contiguous()
+        assert torch.equal(a, b), name

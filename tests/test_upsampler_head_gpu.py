@@ -56,7 +56,7 @@ def test_bicubic_resize_vs_interpolate(h, w, H, W):
 
 @pytest.mark.parametrize('h,w', [(15, 27), (120, 214), (7, 3)])
 def test_pyrup2x_is_the_2x_bicubic_resize(h, w):
-    """The head's first step runs on frtm_pyrup2x (model/seg_network.py: SegNetwork._head_bicubic): at exactly 2x it is the same operator
+    """The head's first step runs on frtm_pyrup2x (model/seg_network.py: SegNetwork._forward_hip): at exactly 2x it is the same operator
     as the bicubic resize, to rounding."""
     from frtm_vos_amd import _hip as Hh
     x = torch.randn(4, h, w, generator=gen(5)).to(DEV)
