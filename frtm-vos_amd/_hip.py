@@ -83,6 +83,7 @@ SIGNATURES = {
     'frtm_conv_last_kernels': (ctypes.c_char_p, []),
     'frtm_conv_bf16x3_launches': (ctypes.c_long, []),
     'frtm_conv_bf16x1_launches': (ctypes.c_long, []),
+    'frtm_conv_bf16x1_3x3_launches': (ctypes.c_long, []),
     'frtm_telea_inpaint_u8': (I, [P, P, I, I, I, I, P]),
     'frtm_fastdiv_check': (ctypes.c_uint, [ctypes.c_uint, ctypes.c_uint]),
     'frtm_backbone_set_lanes': (I, [P, I]),

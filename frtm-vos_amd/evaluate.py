@@ -21,11 +21,15 @@ class AttrDict(dict):
 class Parameters:
 
     def __init__(self, weights=None, fast=False, device='cuda:0', feature_extractor=None, backbone_weights=None, feature_batch=16, trunk_lanes=2,
-                 ytvos_fork_solver=False, refiner_graphs=None, aug_fill='telea', upsampler='compat', trunk_precision='fp32'):
+                 ytvos_fork_solver=False, refiner_graphs=None, aug_fill='telea', upsampler='compat', trunk_precision='fp32',
+                 refiner_precision='fp32'):
         self.device = device
         if trunk_precision not in ('fp32', 'bf16x3', 'bf16x1'):
             raise ValueError("trunk_precision must be 'fp32', 'bf16x3' or 'bf16x1', got %r" % (trunk_precision,))
         self.trunk_precision = trunk_precision    # 'fp32', 'bf16x3' or 'bf16x1': the trunk's routed stride-1 1x1 convs on bf16 pieces (ResnetFeatureExtractor.precision)
+        if refiner_precision not in ('fp32', 'bf16x1'):
+            raise ValueError("refiner_precision must be 'fp32' or 'bf16x1', got %r" % (refiner_precision,))
+        self.refiner_precision = refiner_precision    # 'fp32' or 'bf16x1': the refiner's routed 3x3 convs on one bf16 piece per operand (SegNetwork.precision)
         self.upsampler = upsampler                # refiner head: 'compat' (BackwardCompatibleUpsampler, the reference's default) or 'bicubic'
         #                                           (Upsampler, the head of the YouTube-VOS fork); both load the same checkpoint keys
         self.aug_fill = aug_fill                  # first-frame hole fill: 'telea' (the reference's recipe, on the host; default) or 'pull_push' (device-side substitute of rounds 2-5)
@@ -90,6 +94,7 @@ class Parameters:
         p = self.refnet_params
         chans = {L: n for L, n in extractor.get_out_channels().items() if L in p.layers}
         refiner = self.make_refiner(chans)
+        refiner.precision = self.refiner_precision                 # (after make_refiner: a refiner_factory stand-in gets it too)
         extra = {} if self.refiner_graphs is None else dict(refiner_graphs=bool(self.refiner_graphs))
         mdl = Tracker(augmenter, extractor, self.disc_params, refiner, self.device, feature_batch=self.feature_batch,
                       trunk_lanes=self.trunk_lanes, **extra)
@@ -123,6 +128,9 @@ def parse_args(argv=None):
                     help="'bf16x3': the routed stride-1 1x1 trunk convs on three bf16 pieces per operand (not bitwise fp32: 0.78-1.40x the fp32 kernels' max error against fp64; "
                          "no measurable speed-up of the trunk or the tracker); 'bf16x1': on one bf16 piece per operand, fp32 accumulation (NOT fp32-level arithmetic: "
                          "up to 2^-7 relative error per product); README, DESIGN.md section 4")
+    ap.add_argument('--refiner-precision', choices=['fp32', 'bf16x1'], default='fp32',
+                    help="'bf16x1': the refiner's routed 3x3 convs on one bf16 piece per operand, fp32 accumulation (NOT fp32-level arithmetic: up to 2^-7 "
+                         "relative error per product; the 1x1 convs and the glue stay fp32); README, DESIGN.md section 4")
     ap.add_argument('--dist-backend', default='nccl', help='nccl (= RCCL); gloo for tests')
     ap.add_argument('--share-gpu', action='store_true', help='tests only: every rank uses cuda:0')
     ap.add_argument('--prewarm', default=None, help='HxW: capture the graphs for this frame size (1-3 objects) before the first sequence')
@@ -140,7 +148,7 @@ def parameters_from_args(args, weights):
     """Parameters of a parsed command line (main); the checkpoint `weights` as loaded from --model."""
     return Parameters(weights, fast=args.fast, device=args.dev, ytvos_fork_solver=args.ytvos_solver,
                       refiner_graphs=True if args.refiner_graphs else None, aug_fill='pull_push' if args.pull_push_fill else 'telea',
-                      upsampler=args.upsampler, trunk_precision=args.trunk_precision)
+                      upsampler=args.upsampler, trunk_precision=args.trunk_precision, refiner_precision=args.refiner_precision)
 
 
 def main(argv=None):

@@ -154,17 +154,23 @@ class Upsampler(nn.Module):
 
 
 _HEADS = {'compat': BackwardCompatibleUpsampler, 'bicubic': Upsampler}
+PRECISIONS = ('fp32', 'bf16x1')
 
 
 class SegNetwork(nn.Module):
 
-    def __init__(self, in_channels=1, out_channels=32, ft_channels=None, use_bn=False, upsampler='compat'):
+    def __init__(self, in_channels=1, out_channels=32, ft_channels=None, use_bn=False, upsampler='compat', precision='fp32'):
         """upsampler: 'compat' (BackwardCompatibleUpsampler, the reference's default) or 'bicubic' (Upsampler, the head of its
         YouTube-VOS fork).  The HIP path dispatches on the type of ``self.project``, so assigning ``net.project = Upsampler(...)``
-        afterwards (the reference's commented-out line) works as well."""
+        afterwards (the reference's commented-out line) works as well.
+        precision: 'fp32' (default) or 'bf16x1' -- see the ``precision`` property."""
         if upsampler not in _HEADS:
             raise ValueError('upsampler must be one of %s, not %r' % (sorted(_HEADS), upsampler))
+        if precision not in PRECISIONS:
+            raise ValueError('precision must be one of %s, not %r' % (PRECISIONS, precision))
         super().__init__()
+        self._precision = precision
+        self.bf16_min_blocks = None   # bf16x1 mode: None = the measured routing rule (ops.bf16x1_3x3_launch); a number routes every 3x3 launch of at least that many blocks (0: all)
         assert ft_channels is not None
         self.ft_channels = ft_channels
         self.TSE = nn.ModuleDict()
@@ -189,6 +195,21 @@ class SegNetwork(nn.Module):
         self._pool = None
         self._uses = {}
         self.capture_after = 1           # a (taps, window shape) is replayed as a hipGraph from its (capture_after + 1)-th use on
+
+    @property
+    def precision(self):
+        """'fp32' (default) or 'bf16x1': under 'bf16x1' the inference path (forward on the GPU) runs the 3x3 convs that
+        ops.bf16x1_3x3_launch routes as FRTM_WLAYOUT_BF16X1_3X3 -- operands rounded once to bf16, bf16 MFMAs, fp32 accumulation and epilogue
+        (csrc/conv3x3_bf16x1.hip).  The 1x1 convs and the glue kernels stay fp32, and so do forward_torch and forward_train.  Setting it
+        drops the packed weights and captured graphs of the other mode."""
+        return self._precision
+
+    @precision.setter
+    def precision(self, value):
+        if value not in PRECISIONS:
+            raise ValueError('precision must be one of %s, not %r' % (PRECISIONS, value))
+        self._precision = value
+        self.invalidate()
 
     def invalidate(self):
         """Drop the packed HIP weights and captured graphs (call after editing parameters in place)."""
@@ -326,8 +347,9 @@ class SegNetwork(nn.Module):
             if shift is not None and scale is None:
                 scale = torch.ones(cout, device=dev)
             wW = ops.pack_weights(m.weight.data, wino=True)[0] if m.weight.shape[2] == 3 else None      # Winograd image of the 3x3s
+            wB = ops.pack_weights(m.weight.data, bf16x1=True)[0] if (m.weight.shape[2] == 3 and self._precision == 'bf16x1') else None
             return dict(wT=wT, ktab=ktab, lay=lay, cout=cout, k=m.weight.shape[2], scale=None if scale is None else scale.contiguous(),
-                        shift=None if shift is None else shift.contiguous(), relu=relu_, wW=wW)
+                        shift=None if shift is None else shift.contiguous(), relu=relu_, wW=wW, wB=wB, cin=m.weight.shape[1])
 
         def rrb(m):
             first = m.bblock[0]
@@ -367,6 +389,11 @@ class SegNetwork(nn.Module):
         return P
 
     def _conv(self, x, c, residual=None):
+        if c.get('wB') is not None:               # bf16x1 mode: the 3x3 launches that the one rule of ops.py routes
+            n, _, hh, ww = x.shape
+            if ops.bf16x1_3x3_launch(n, hh, ww, c['cin'], c['cout'], self.bf16_min_blocks):
+                return ops.conv2d(x, c['wB'], c['cout'], 3, 1, 1, scale=c['scale'], shift=c['shift'], residual=residual,
+                                  relu=c['relu'], splitk=1, w_layout=7)
         if c.get('wW') is not None and self.use_winograd:
             n, _, hh, ww = x.shape
             if ops.wino_launch(n, hh, ww, c['cout']):

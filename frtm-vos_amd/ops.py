@@ -47,16 +47,26 @@ def bf16x1_elems(Cout, Cin):
     return ((Cin + 15) // 16 * 16) * ((Cout + 127) // 128 * 128) // 2
 
 
+def bf16x1_3x3_elems(Cout, Cin):
+    """Floats of a FRTM_WLAYOUT_BF16X1_3X3 image (FRTM_CONV_BF16X1_3X3_ELEMS): bf16 [Cin/16][tap][2][Mp][8], Mp = Cout rounded up to 32."""
+    return 9 * ((Cin + 15) // 16 * 16) * ((Cout + 31) // 32 * 32) // 2
+
+
 def pack_weights(w_oihw, halo=None, wino=False, wino4=False, wino6=False, bf16x3=False, bf16x1=False):
     """(Cout,Cin,k,k) -> packed GEMM weights (+ ktab for k > 1).  3x3 kernels default to the halo layout
     (valid for pad-1 convs of stride 1 or 2); wino=True: Winograd F(2x2,3x3) image (stride 1, pad 1); wino4=True: the 36 transformed
     weight matrices of Winograd F(4x4,3x3) (FRTM_WLAYOUT_WINO4; conv2d then needs ``ws`` = wino4_workspace(...)); wino6=True: the 64 of
     F(6x6,3x3) (FRTM_WLAYOUT_WINO6, ``ws`` = wino4_workspace(..., m=6)); bf16x3=True: the three bf16 pieces of a 1x1 kernel (FRTM_WLAYOUT_BF16X3,
     Cin % 16 == 0; conv2d with ``w_layout=5``); bf16x1=True: the weights rounded to one bf16 plane (FRTM_WLAYOUT_BF16X1, Cin % 16 == 0; conv2d with
-    ``w_layout=6``, ``tile`` 0 = automatic, 1 = 128x64, 2 = 64x64).
+    ``w_layout=6``, ``tile`` 0 = automatic, 1 = 128x64, 2 = 64x64) -- or, for a 3x3 kernel, the bf16 image of the direct 3x3 form
+    (FRTM_WLAYOUT_BF16X1_3X3, any Cin; conv2d with ``w_layout=7``, stride 1, pad 1, ``tile`` 0 = automatic, 1 = 64, 2 = 96 output channels).
     Returns (wT, ktab, layout)."""
     w = w_oihw.detach().float().contiguous()
     Cout, Cin, k, _ = w.shape
+    if bf16x1 and k == 3:
+        wT = torch.zeros(bf16x1_3x3_elems(Cout, Cin), device=w.device)
+        H.call('frtm_conv_pack_weights', H.ptr(w), Cout, Cin, k, 7, H.ptr(wT), None)
+        return wT, None, 7
     if bf16x1:
         wT = torch.zeros(bf16x1_elems(Cout, Cin), device=w.device)
         H.call('frtm_conv_pack_weights', H.ptr(w), Cout, Cin, k, 6, H.ptr(wT), None)
@@ -188,6 +198,22 @@ def wino_launch(n, h, w, cout):
     """The Winograd launch rule of the refiner's 3x3 convs (the trunk's: csrc/backbone.hip): F(2x2,3x3) when the launch has at least
     FRTM_WINO_MIN_BLOCKS 8x8 output blocks x 32-channel tiles, below that the halo layout with split-K."""
     return n * ((h + 7) // 8) * ((w + 7) // 8) * ((cout + 31) // 32) >= WINO_MIN_BLOCKS
+
+
+def bf16x1_3x3_launch(n, h, w, cin, cout, min_blocks=None):
+    """The ONE rule by which a bf16x1 refiner (SegNetwork.precision = 'bf16x1') routes a 3x3 conv to FRTM_WLAYOUT_BF16X1_3X3.
+    ``min_blocks`` None: the measured rule (profiles/bf16x1_refiner_time.txt) -- BF16X1_3X3_ROUTES: a (cin, cout) pair is routed from the block
+    count (wino_launch's count) of its smallest measured launch from which every measured launch's bf16 median beat the fp32 median by more than
+    the fp32 arm's spread; only launches that wino_launch accepts were measured, so nothing below WINO_MIN_BLOCKS is routed.  A number: every
+    3x3 conv whose launch has at least that many blocks (0 routes everything -- tests on small maps)."""
+    blocks = n * ((h + 7) // 8) * ((w + 7) // 8) * ((cout + 31) // 32)
+    if min_blocks is not None:
+        return blocks >= min_blocks
+    return blocks >= max(WINO_MIN_BLOCKS, BF16X1_3X3_ROUTES.get((cin, cout), 1 << 62))
+
+
+# (cin, cout) -> fewest blocks per launch from which the measurement routes the refiner's 3x3 convs (see bf16x1_3x3_launch)
+BF16X1_3X3_ROUTES = {(64, 64): 896, (65, 65): 5376, (65, 64): 12960, (64, 65): 9720, (64, 32): 25920}
 
 
 def _refuse(fn, why, **tensors):

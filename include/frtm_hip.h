@@ -314,6 +314,17 @@ typedef struct {
 #define FRTM_CONV_BF16X1_ELEMS(Cout, Cin) ((size_t)(((Cin) + 15) / 16 * 16) * (((Cout) + 127) / 128 * 128) / 2)
 #define FRTM_BF16X1_TILE_128x64 1
 #define FRTM_BF16X1_TILE_64x64 2
+/* bf16x1 for 3x3 convs (opt-in refiner precision mode, csrc/conv3x3_bf16x1.hip): 3x3, stride 1, pad 1 (zeros), NCHW output, w_pitch 0, splitk 0 or 1;
+   any Cin, Cout, B, H, W.  The arithmetic and semantics of FRTM_WLAYOUT_BF16X1 in the direct form: out = epilogue(sum bf16(W) * bf16(X)), operands
+   rounded once to nearest even, bf16 MFMAs, fp32 accumulation and epilogue; element-wise |out - exact| <= (2^-7 + 2^-16 + K 2^-22) |scale| (|W| conv |X|)
+   with K = 9 Cin, plus the epilogue's fp32 rounding.  NaN stays NaN, Inf stays Inf; padding is zeros on both operands.  Deterministic, and independent of
+   the tile form and the grid.  `tile`: 0 = automatic (the form with fewer padded rows), or FRTM_BF16X1_3X3_TILE_64 (1), FRTM_BF16X1_3X3_TILE_96 (2): output
+   channels per workgroup, on 8 x 32 pixels.  The image is bf16 [Cin/16][tap][2][Mp][8], Mp = Cout rounded up to 32, in a float buffer of
+   FRTM_CONV_BF16X1_3X3_ELEMS floats (16-byte aligned).  Other descriptors return FRTM_ERR_ARG.  FRTM_WLAYOUT_BF16X1 (6) keeps refusing 3x3 kernels. */
+#define FRTM_WLAYOUT_BF16X1_3X3 7
+#define FRTM_CONV_BF16X1_3X3_ELEMS(Cout, Cin) ((size_t)9 * (((Cin) + 15) / 16 * 16) * (((Cout) + 31) / 32 * 32) / 2)
+#define FRTM_BF16X1_3X3_TILE_64 1
+#define FRTM_BF16X1_3X3_TILE_96 2
 #define FRTM_WINO_MIN_BLOCKS 512   /* 8x8 output blocks x 32-channel tiles below which callers prefer HALO3X3 + split-K */
 #define FRTM_CONV_PACKED_ELEMS(Cout, Cin, k) \
   (((((Cin) * (k) * (k) + 31) / 32 * 32) > (((Cin) + 7) / 8 * 72) ? (((Cin) * (k) * (k) + 31) / 32 * 32) : (((Cin) + 7) / 8 * 72)) * (((Cout) + 31) / 32 * 32))
@@ -392,6 +403,8 @@ const char* frtm_conv_last_kernels(void);
 long frtm_conv_bf16x3_launches(void);
 /* ... and that took the bf16x1 form (FRTM_WLAYOUT_BF16X1, csrc/conv_bf16x1.hip).  The two counters are disjoint. */
 long frtm_conv_bf16x1_launches(void);
+/* ... and that took the bf16x1 3x3 form (FRTM_WLAYOUT_BF16X1_3X3, csrc/conv3x3_bf16x1.hip): a counter of its own, the 1x1 counter does not move. */
+long frtm_conv_bf16x1_3x3_launches(void);
 /* Host-side check of the multiplication the conv kernels use instead of integer divisions in their index arithmetic (csrc/conv_common.h: FastDiv,
  * q = (mulhi(n, m) + n) >> s with m, s prepared per divisor): returns n / d as that formula computes it, for 0 <= n < 2^31, d >= 1.
  * No GPU involved; tests/test_cpu_host.py sweeps it against Python's integer division. */
