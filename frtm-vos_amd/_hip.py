@@ -104,6 +104,9 @@ SIGNATURES = {
     'frtm_plane_mean': (I, [P, I, I, P, P]),
     'frtm_conv_wgrad_ws_elems': (ctypes.c_size_t, [I, I, I, I, I, I]),
     'frtm_conv_wgrad': (I, [P, P, I, I, I, I, I, I, P, P, P, ctypes.c_size_t, P]),
+    'frtm_conv_wgrad_bf16x1_ws_elems': (ctypes.c_size_t, [I, I, I, I, I]),
+    'frtm_conv_wgrad_bf16x1': (I, [P, P, I, I, I, I, I, P, P, P, ctypes.c_size_t, P]),
+    'frtm_conv_wgrad_bf16x1_launches': (ctypes.c_long, []),
     'frtm_bn_stats': (I, [P, I, I, I, F, F, I, P, P, P, P, P, P]),
     'frtm_bn_apply_relu': (I, [P, P, P, P, P, I, I, I, P, P]),
     'frtm_bn_relu_backward': (I, [P, P, P, P, P, P, I, I, I, I, P, P, P, P, P]),

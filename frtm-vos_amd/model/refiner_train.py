@@ -11,6 +11,10 @@ Its backward (csrc/refiner_train.hip) gives the gradient of every parameter that
     32-channel full-resolution tensor of the head is neither formed nor kept (the identity of frtm_tap_mix).
 No sum uses atomics, so two identical backward passes give bitwise identical gradients.  No gradient flows into the scores or the
 backbone taps (the input gradient of TSE.reduce[0] is not computed).
+
+Under ``SegNetwork.train_precision = 'bf16x1'`` the 3x3 forward and input-gradient convs that ops.bf16x1_3x3_launch routes and the 3x3 weight
+gradients that ops.bf16x1_wgrad_launch routes run on the bf16 form (operands rounded once to bf16, bf16 MFMAs, fp32 accumulation); everything
+else -- 1x1 convs and their gradients, BatchNorm, the glue kernels, the head's tap-map weight gradient, what is saved -- stays fp32.
 """
 import torch
 from torch import nn
@@ -30,6 +34,7 @@ class _Runner:
 
     def __init__(self, net, dev):
         self.net, self.dev = net, dev
+        self.bf16 = net.train_precision == 'bf16x1'
         self._ones = {}
 
     def ones(self, c):
@@ -42,7 +47,10 @@ class _Runner:
         cout, k = w.shape[0], w.shape[2]
         shift = None if bias is None else bias.detach().float().contiguous()
         scale = None if shift is None else self.ones(cout)
-        n, _, hh, ww = x.shape
+        n, cin, hh, ww = x.shape
+        if k == 3 and self.bf16 and ops.bf16x1_3x3_launch(n, hh, ww, cin, cout, self.net.bf16_min_blocks):
+            wB = ops.pack_weights(w, bf16x1=True)[0]
+            return ops.conv2d(x, wB, cout, 3, 1, 1, scale=scale, shift=shift, residual=residual, relu=relu, splitk=1, w_layout=7)
         if k == 3 and self.net.use_winograd and ops.wino_launch(n, hh, ww, cout):
             wW = ops.pack_weights(w, wino=True)[0]
             return ops.conv2d(x, wW, cout, 3, 1, 1, scale=scale, shift=shift, residual=residual, relu=relu, splitk=1, w_layout=2)
@@ -50,7 +58,8 @@ class _Runner:
         return ops.conv2d(x, wT, cout, k, 1, k // 2, ktab=ktab, scale=scale, shift=shift, residual=residual, relu=relu, w_layout=lay)
 
     def dgrad(self, dy, w, residual=None, rows=None):
-        """Input gradient of a stride-1 conv; ``rows``: only the first input channels."""
+        """Input gradient of a stride-1 conv; ``rows``: only the first input channels.  A forward conv of the transposed channel pair: conv's
+        routing rules see (Cout, Cin or rows)."""
         wt = _flipT(w) if w.shape[2] == 3 else w.detach().transpose(0, 1).contiguous()
         if rows is not None:
             wt = wt[:rows].contiguous()
@@ -93,7 +102,9 @@ def _cab_weights(cab):
 class _Grads:
     """Collects parameter gradients by identity; ``want(p)``: whether p needs one."""
 
-    def __init__(self, params, needs):
+    def __init__(self, params, needs, net=None):
+        self.bf16 = net is not None and net.train_precision == 'bf16x1'
+        self.min_blocks = None if net is None else net.bf16_min_blocks
         self.index = {id(p): i for i, p in enumerate(params)}
         self.needs = needs
         self.out = [None] * len(params)
@@ -109,7 +120,10 @@ class _Grads:
         """weight / bias gradients of conv module m (skipped when frozen)."""
         ww, wb = self.want(m.weight), self.want(m.bias)
         if ww or wb:
-            dw, db = ops.conv_wgrad(dy, x, m.weight.shape[2], weight=ww, bias=wb)
+            k = m.weight.shape[2]
+            n, cout, hh, wd = dy.shape
+            bf = k == 3 and self.bf16 and ops.bf16x1_wgrad_launch(n, hh, wd, x.shape[1], cout, self.min_blocks)
+            dw, db = ops.conv_wgrad(dy, x, k, weight=ww, bias=wb, bf16x1=bf)
             self.put(m.weight, dw)
             self.put(m.bias, db)
 
@@ -177,7 +191,7 @@ class _RefinerTrain(torch.autograd.Function):
         net, sv = ctx.net, ctx.sv
         params = ctx.params
         n_feat = len(net.ft_channels)
-        G = _Grads(params, ctx.needs_input_grad[4 + n_feat:])
+        G = _Grads(params, ctx.needs_input_grad[4 + n_feat:], net)
         R = _Runner(net, dlogits.device)
         levels = list(net.ft_channels)
         dl = dlogits.detach().float().contiguous()

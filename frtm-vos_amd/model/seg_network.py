@@ -159,18 +159,22 @@ PRECISIONS = ('fp32', 'bf16x1')
 
 class SegNetwork(nn.Module):
 
-    def __init__(self, in_channels=1, out_channels=32, ft_channels=None, use_bn=False, upsampler='compat', precision='fp32'):
+    def __init__(self, in_channels=1, out_channels=32, ft_channels=None, use_bn=False, upsampler='compat', precision='fp32', train_precision='fp32'):
         """upsampler: 'compat' (BackwardCompatibleUpsampler, the reference's default) or 'bicubic' (Upsampler, the head of its
         YouTube-VOS fork).  The HIP path dispatches on the type of ``self.project``, so assigning ``net.project = Upsampler(...)``
         afterwards (the reference's commented-out line) works as well.
-        precision: 'fp32' (default) or 'bf16x1' -- see the ``precision`` property."""
+        precision: 'fp32' (default) or 'bf16x1' -- see the ``precision`` property (the inference path).
+        train_precision: 'fp32' (default) or 'bf16x1' -- see the ``train_precision`` property (forward_train); independent of ``precision``."""
         if upsampler not in _HEADS:
             raise ValueError('upsampler must be one of %s, not %r' % (sorted(_HEADS), upsampler))
         if precision not in PRECISIONS:
             raise ValueError('precision must be one of %s, not %r' % (PRECISIONS, precision))
+        if train_precision not in PRECISIONS:
+            raise ValueError('train_precision must be one of %s, not %r' % (PRECISIONS, train_precision))
         super().__init__()
         self._precision = precision
-        self.bf16_min_blocks = None   # bf16x1 mode: None = the measured routing rule (ops.bf16x1_3x3_launch); a number routes every 3x3 launch of at least that many blocks (0: all)
+        self._train_precision = train_precision
+        self.bf16_min_blocks = None   # bf16x1 modes: None = the measured routing rules (ops.bf16x1_3x3_launch, ops.bf16x1_wgrad_launch); a number routes every 3x3 launch of at least that many blocks (0: all)
         assert ft_channels is not None
         self.ft_channels = ft_channels
         self.TSE = nn.ModuleDict()
@@ -210,6 +214,23 @@ class SegNetwork(nn.Module):
             raise ValueError('precision must be one of %s, not %r' % (PRECISIONS, value))
         self._precision = value
         self.invalidate()
+
+    @property
+    def train_precision(self):
+        """'fp32' (default) or 'bf16x1': the arithmetic of forward_train, independent of ``precision``.  Under 'bf16x1' the training pass runs
+        on the bf16 form (operands rounded once to bf16, bf16 MFMAs, fp32 accumulation): the 3x3 forward and input-gradient convs that
+        ops.bf16x1_3x3_launch routes (csrc/conv3x3_bf16x1.hip, weights packed per call; the input gradient under the transposed channel pair)
+        and the 3x3 weight gradients that ops.bf16x1_wgrad_launch routes (csrc/conv_wgrad_bf16x1.hip); ``bf16_min_blocks`` applies to all
+        three.  The 1x1 convs and their gradients, BatchNorm, the glue kernels, the head's tap-map weight gradient, the master weights, the
+        saved activations and forward_torch stay fp32.  Nothing is cached per mode: setting it touches neither the packed inference weights
+        nor the captured graphs."""
+        return self._train_precision
+
+    @train_precision.setter
+    def train_precision(self, value):
+        if value not in PRECISIONS:
+            raise ValueError('train_precision must be one of %s, not %r' % (PRECISIONS, value))
+        self._train_precision = value
 
     def invalidate(self):
         """Drop the packed HIP weights and captured graphs (call after editing parameters in place)."""
@@ -275,7 +296,8 @@ class SegNetwork(nn.Module):
         """The training pass on the HIP kernels (model/refiner_train.py): logits (N,1,H,W) equal to forward_torch(...) for the same module
         state, with a grad_fn whose backward writes (accumulates) .grad of every refiner parameter that requires grad.  BatchNorm uses
         batch statistics and updates the running ones in train mode, the running statistics in eval mode.  One object per frame
-        (scores (N,1,h,w), taps (N,C,H,W)); the compat head only; no gradient into scores or taps (they must not require grad)."""
+        (scores (N,1,h,w), taps (N,C,H,W)); the compat head only; no gradient into scores or taps (they must not require grad).
+        fp32 whatever ``precision`` says; ``train_precision`` = 'bf16x1' puts its 3x3 convs and weight gradients on the bf16 form."""
         from .refiner_train import forward_train
         return forward_train(self, scores, features, image_size)
 

@@ -213,7 +213,8 @@ def bf16x1_3x3_launch(n, h, w, cin, cout, min_blocks=None):
 
 
 # (cin, cout) -> fewest blocks per launch from which the measurement routes the refiner's 3x3 convs (see bf16x1_3x3_launch)
-BF16X1_3X3_ROUTES = {(64, 64): 896, (65, 65): 5376, (65, 64): 12960, (64, 65): 9720, (64, 32): 25920}
+# (32, 64): the input gradient of the head's conv1 in a bf16x1 training pass (profiles/bf16x1_refiner_train_time.txt)
+BF16X1_3X3_ROUTES = {(64, 64): 896, (65, 65): 5376, (65, 64): 12960, (64, 65): 9720, (64, 32): 25920, (32, 64): 51840}
 
 
 def _refuse(fn, why, **tensors):
@@ -348,19 +349,41 @@ def project_tail(y, w3x3, bias, size, bicubic=False):
 # ----------------------------------------------------------------------------------------------------------------------
 # Refiner training (csrc/refiner_train.hip; model/refiner_train.py)
 # ----------------------------------------------------------------------------------------------------------------------
-def conv_wgrad(dy, x, k, weight=True, bias=True):
+def conv_wgrad(dy, x, k, weight=True, bias=True, bf16x1=False):
     """Gradients of a stride-1, pad-k//2 conv (k = 1 or 3) from its output gradient dy (B,Cout,H,W) and input x (B,Cin,H,W):
-    (dW (Cout,Cin,k,k) or None, dbias (Cout) or None).  Deterministic: fixed-order sums, no atomics."""
+    (dW (Cout,Cin,k,k) or None, dbias (Cout) or None).  Deterministic: fixed-order sums, no atomics.  ``bf16x1`` (k = 3 only): the bf16x1
+    form (frtm_conv_wgrad_bf16x1: both operands rounded to bf16 once, bf16 MFMAs, fp32 accumulation) -- NOT fp32-level arithmetic."""
     B, Cout, Hh, Ww = dy.shape
     Cin = x.shape[1]
     assert tuple(x.shape) == (B, Cin, Hh, Ww) and (weight or bias)
-    elems = H.lib().frtm_conv_wgrad_ws_elems(B, Cout, Cin, k, Hh, Ww)
+    if bf16x1 and k != 3:
+        raise ValueError('conv_wgrad: the bf16x1 form is a 3x3 weight gradient (k = 3), got k = %d' % k)
+    elems = H.lib().frtm_conv_wgrad_bf16x1_ws_elems(B, Cout, Cin, Hh, Ww) if bf16x1 else H.lib().frtm_conv_wgrad_ws_elems(B, Cout, Cin, k, Hh, Ww)
     # its own slab buffer: growing the shared conv workspace would change the split-K factor frtm_conv2d picks for later convs
     ws = torch.empty(elems, device=dy.device)
     dw = torch.empty(Cout, Cin, k, k, device=dy.device) if weight else None
     db = torch.empty(Cout, device=dy.device) if bias else None
-    H.call('frtm_conv_wgrad', H.ptr(dy), H.ptr(x), B, Cout, Cin, k, Hh, Ww, H.ptr(dw), H.ptr(db), H.ptr(ws), ws.numel())
+    if bf16x1:
+        H.call('frtm_conv_wgrad_bf16x1', H.ptr(dy), H.ptr(x), B, Cout, Cin, Hh, Ww, H.ptr(dw), H.ptr(db), H.ptr(ws), ws.numel())
+    else:
+        H.call('frtm_conv_wgrad', H.ptr(dy), H.ptr(x), B, Cout, Cin, k, Hh, Ww, H.ptr(dw), H.ptr(db), H.ptr(ws), ws.numel())
     return dw, db
+
+
+def bf16x1_wgrad_launch(B, h, w, cin, cout, min_blocks=None):
+    """The ONE rule by which a bf16x1 refiner training pass (SegNetwork.train_precision = 'bf16x1') routes a 3x3 weight gradient to
+    frtm_conv_wgrad_bf16x1.  The block count is bf16x1_3x3_launch's, of the conv whose gradient it is.  ``min_blocks`` None: the measured rule
+    (profiles/bf16x1_refiner_train_time.txt) -- BF16X1_WGRAD_ROUTES: a (cin, cout) pair is routed from the block count of its smallest measured
+    launch from which every measured launch's bf16 median beat the fp32 median by more than the fp32 arm's spread; an unmeasured pair stays
+    fp32.  A number: every 3x3 weight gradient whose conv has at least that many blocks (0 routes everything -- tests on small maps)."""
+    blocks = B * ((h + 7) // 8) * ((w + 7) // 8) * ((cout + 31) // 32)
+    if min_blocks is not None:
+        return blocks >= min_blocks
+    return blocks >= BF16X1_WGRAD_ROUTES.get((cin, cout), 1 << 62)
+
+
+# (cin, cout) -> fewest blocks from which the measurement routes the refiner's 3x3 weight gradients (see bf16x1_wgrad_launch)
+BF16X1_WGRAD_ROUTES = {(64, 32): 128, (64, 64): 896, (65, 64): 896, (65, 65): 384}
 
 
 def bn_stats(x, running_mean, running_var, eps, factor, train):

@@ -26,8 +26,15 @@ class ModelParameters:
     """The training configuration of the reference (train.py:23-92): 15 augmentations of the first frame, a 32-channel target model
     without pixel weighting, the 64-channel refiner with BatchNorm."""
 
-    def __init__(self, name, feature_extractor='resnet101', device='cuda:0', batch_size=None, tmodel_cache_path=None):
+    def __init__(self, name, feature_extractor='resnet101', device='cuda:0', batch_size=None, tmodel_cache_path=None, trunk_precision='fp32',
+                 refiner_precision='fp32'):
         self.name, self.device, self.batch_size = name, device, batch_size
+        if trunk_precision not in ('fp32', 'bf16x3', 'bf16x1'):
+            raise ValueError("trunk_precision must be 'fp32', 'bf16x3' or 'bf16x1', got %r" % (trunk_precision,))
+        self.trunk_precision = trunk_precision        # the frozen trunk's routed 1x1 convs on bf16 pieces (ResnetFeatureExtractor.precision)
+        if refiner_precision not in ('fp32', 'bf16x1'):
+            raise ValueError("refiner_precision must be 'fp32' or 'bf16x1', got %r" % (refiner_precision,))
+        self.refiner_precision = refiner_precision    # the refiner's training pass: its routed 3x3 convs and weight gradients on bf16 (SegNetwork.train_precision)
         self.feature_extractor = feature_extractor
         self.aug_params = AttrDict(
             num_aug=15, min_px_count=1,
@@ -54,12 +61,12 @@ class ModelParameters:
         from .model.seg_network import SegNetwork
         from .model.training_model import TrainerModel
         augmenter = ImageAugmenter(self.aug_params)
-        extractor = ResnetFeatureExtractor(self.feature_extractor).to(self.device)       # weights: FRTM_RESNET_WEIGHTS, else seeded synthetic ones
+        extractor = ResnetFeatureExtractor(self.feature_extractor, precision=self.trunk_precision).to(self.device)       # weights: FRTM_RESNET_WEIGHTS, else seeded synthetic ones
         p = self.refnet_params
         chans = {L: n for L, n in extractor.get_out_channels().items() if L in p.refinement_layers}
         self.disc_params.in_channels = extractor.get_out_channels()[self.disc_params.layer]
         torch.manual_seed(1)                                       # seeded default init, as evaluate.Parameters.make_refiner
-        refiner = SegNetwork(1, p.nchannels, chans, p.use_batch_norm).to(self.device)
+        refiner = SegNetwork(1, p.nchannels, chans, p.use_batch_norm, train_precision=self.refiner_precision).to(self.device)
         return TrainerModel(augmenter, extractor, self.disc_params, refiner, batch_size=self.batch_size, tmodel_cache=self.tmodel_cache,
                             device=self.device, refiner_backend='hip', loss_backend='hip')
 
@@ -80,6 +87,11 @@ def parse_args(argv=None):
     ap.add_argument('--workspace', default='workspace', help='checkpoints/, logs/ and tmodels_cache/ are created below it')
     ap.add_argument('--synthetic-sequences', type=int, default=32)
     ap.add_argument('--synthetic-size', default='480x854', help='HxW of the synthetic frames')
+    ap.add_argument('--trunk-precision', choices=['fp32', 'bf16x3', 'bf16x1'], default='fp32',
+                    help="the frozen trunk's routed 1x1 convs: fp32, three bf16 pieces (fp32-level) or one bf16 piece (NOT fp32-level)")
+    ap.add_argument('--refiner-precision', choices=['fp32', 'bf16x1'], default='fp32',
+                    help="the refiner's training pass: bf16x1 runs the routed 3x3 convs, input and weight gradients on bf16 MFMAs with fp32 "
+                         "accumulation (NOT fp32-level; master weights, BatchNorm, 1x1 convs and checkpoints stay fp32)")
     return ap.parse_args(argv)
 
 
@@ -117,7 +129,7 @@ def main(argv=None):
         dataset = file_datasets(args, ws)
         hooks = dict(collate_fn=raw_collate, batch_transform=DeviceFrameResizer((480, 854), args.dev, datasets=dataset))
     params = ModelParameters(args.name, feature_extractor=args.ftext, device=args.dev, tmodel_cache_path=ws / 'tmodels_cache',
-                             batch_size=args.batch_size)
+                             batch_size=args.batch_size, trunk_precision=args.trunk_precision, refiner_precision=args.refiner_precision)
     model = params.get_model()
     optimizer = FusedAdam(model.refiner.parameters(), lr=1e-3, betas=(0.9, 0.999), weight_decay=1e-5, amsgrad=True)
     scheduler = torch.optim.lr_scheduler.StepLR(optimizer, step_size=127, gamma=0.1)

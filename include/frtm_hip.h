@@ -524,6 +524,15 @@ int frtm_plane_mean(const float* in, int planes, int HW, float* out, frtm_stream
 size_t frtm_conv_wgrad_ws_elems(int B, int Cout, int Cin, int k, int H, int W);
 int frtm_conv_wgrad(const float* dy, const float* x, int B, int Cout, int Cin, int k, int H, int W, float* dw, float* dbias, float* ws,
                     size_t ws_elems, frtm_stream_t stream);
+/* The same for k = 3 in bf16x1 arithmetic (csrc/conv_wgrad_bf16x1.hip; the opt-in SegNetwork.train_precision = 'bf16x1'): dy and x are each rounded
+ * to bf16 once, to nearest even, the products run on v_mfma_f32_32x32x16_bf16, accumulation is fp32 in chains of at most 2048 pixels, and the
+ * chains' slabs in ws (>= frtm_conv_wgrad_bf16x1_ws_elems floats) are summed in fp64 in a fixed order.  dbias is the ones column of the same
+ * product: the sum of bf16(dy).  Up to 2^-7 of |dy| (x) |x| per element: NOT fp32-level arithmetic.  No atomics; the arguments as above. */
+size_t frtm_conv_wgrad_bf16x1_ws_elems(int B, int Cout, int Cin, int H, int W);
+int frtm_conv_wgrad_bf16x1(const float* dy, const float* x, int B, int Cout, int Cin, int H, int W, float* dw, float* dbias, float* ws,
+                           size_t ws_elems, frtm_stream_t stream);
+/* Launches of frtm_conv_wgrad_bf16x1 (this process), like frtm_conv_bf16x1_3x3_launches. */
+long frtm_conv_wgrad_bf16x1_launches(void);
 /* BatchNorm2d statistics of x (N,C,HW).  train = 1: batch mean and 1/sqrt(biased var + eps) -> mean, invstd; when rmean / rvar are
  * given, they are updated as nn.BatchNorm2d does with factor = momentum (or 1/num_batches_tracked for momentum=None; 0: no update),
  * unbiased variance.  part: >= 2*N*C doubles.  train = 0: mean = rmean, invstd = 1/sqrt(rvar + eps) (part unused). */
