@@ -147,6 +147,7 @@ SIGNATURES = {
     'frtm_adam_chunk_elems': (I, []),
     'frtm_adam_amsgrad': (I, [P, I, P, I, D, D, D, D, D, D, D, I, P]),
     'frtm_resize_frames_u8': (I, [P, ctypes.c_size_t, P, P, I, I, P, I, I, P]),
+    'frtm_target_apply_grouped': (I, [P, ctypes.c_size_t, I, P, P, P, I, I, I, I, I, P, P, P]),
     'frtm_resize_labels_u8': (I, [P, ctypes.c_size_t, P, P, I, P, I, I, P]),
 }
 

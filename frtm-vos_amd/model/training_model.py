@@ -25,6 +25,7 @@ from pathlib import Path
 import torch
 import torch.nn as nn
 
+from .. import _hip as H
 from ..lib.utils import interpolate
 from .discriminator import Discriminator
 from .train_loss import bce_logits_stats, iou_from_counts
@@ -107,6 +108,7 @@ class TargetModelBank:
     def __init__(self, disc_params, size):
         self.slots = [_FrozenTarget(disc_params) for _ in range(size)]
         self.layer = disc_params['layer']
+        self._grouped = None        # scores(grouped=True): pointer tables and the projected-feature workspace
 
     @torch.no_grad()
     def fit_or_load(self, images, labels, specs, cache, augment, extractor, device):
@@ -125,9 +127,34 @@ class TargetModelBank:
         return hits
 
     @torch.no_grad()
-    def scores(self, layer_features):
-        """(B,Cin,h,w) -> (B,1,h,w): sample i scored by target model i."""
-        return torch.cat([slot.discriminator.apply(layer_features[i:i + 1]) for i, slot in enumerate(self.slots[:layer_features.shape[0]])])
+    def scores(self, layer_features, grouped=False):
+        """(B,Cin,h,w) -> (B,1,h,w): sample i scored by target model i.  ``grouped``: one ops.target_apply_grouped call over the B
+        pairs (frame i, slot i) instead of B times Discriminator.apply (three small launches each)."""
+        if not grouped:
+            return torch.cat([slot.discriminator.apply(layer_features[i:i + 1]) for i, slot in enumerate(self.slots[:layer_features.shape[0]])])
+        from .. import ops
+        H.require_gpu(layer_features, 'TargetModelBank.scores')
+        B = layer_features.shape[0]
+        discs = [slot.discriminator for slot in self.slots[:B]]
+        dev = layer_features.device
+        c = discs[0].project.out_channels
+        ptrs = [d._project_T().data_ptr() for d in discs] + [d.filter.weight.data_ptr() for d in discs]
+        g = self._grouped
+        if g is None or g['ptrs'] != ptrs or g['dev'] != dev:
+            # the tables change when a slot is re-fitted or re-loaded (its GEMM-layout projection is a new tensor), not per frame
+            g = self._grouped = dict(ptrs=ptrs, dev=dev, cft=None if g is None or g['dev'] != dev else g['cft'],
+                                     w1T=ops.pointer_table([d._project_T() for d in discs], dev),
+                                     w2=ops.pointer_table([d.filter.weight.data for d in discs], dev),
+                                     frames=H.upload(torch.arange(B, dtype=torch.int32), dev))
+        shape = (B, c) + tuple(layer_features.shape[-2:])
+        if g['cft'] is None or tuple(g['cft'].shape) != shape:
+            g['cft'] = torch.empty(shape, device=dev)                # reused workspace: the projected features are not kept in training
+        feats = layer_features if layer_features[0].is_contiguous() else layer_features.contiguous()
+        cft, scores = ops.target_apply_grouped(feats, g['frames'], g['w1T'], g['w2'], c, cft=g['cft'])
+        for i, d in enumerate(discs):                                 # the bookkeeping of Discriminator.apply
+            d.frame_num += 1
+            d.current_sample = cft[i:i + 1]
+        return scores
 
 
 def mask_iou(pred, gt):
@@ -141,11 +168,13 @@ def mask_iou(pred, gt):
 class TrainerModel(nn.Module):
 
     def __init__(self, augmenter, feature_extractor, disc_params, seg_network, batch_size=0, tmodel_cache=None, device=None,
-                 refiner_backend='torch', loss_backend='torch'):
+                 refiner_backend='torch', loss_backend='torch', batched_scores=False):
         """refiner_backend: 'torch' runs the refiner's training pass through its PyTorch definition (forward_torch), 'hip' through
         SegNetwork.forward_train (HIP kernels forward and backward).
         loss_backend: 'torch' = sigmoid + nn.BCELoss + mask_iou on framework kernels, read back after every frame; 'hip' = the
-        loss tail of model/train_loss.py on the logits, statistics accumulated on the device and read back once per call."""
+        loss tail of model/train_loss.py on the logits, statistics accumulated on the device and read back once per call.
+        batched_scores: the B target models of a batch score their frames in one grouped launch (TargetModelBank.scores(grouped=True))
+        instead of one Discriminator.apply per sample."""
         if refiner_backend not in ('torch', 'hip'):
             raise ValueError("refiner_backend must be 'torch' or 'hip', not %r" % (refiner_backend,))
         if loss_backend not in ('torch', 'hip'):
@@ -153,6 +182,7 @@ class TrainerModel(nn.Module):
         super().__init__()
         self.refiner_backend = refiner_backend
         self.loss_backend = loss_backend
+        self.batched_scores = bool(batched_scores)
         self.augmenter = augmenter
         self.feature_extractor = feature_extractor
         self.refiner = seg_network
@@ -184,7 +214,7 @@ class TrainerModel(nn.Module):
         frozen on the HIP path, the refiner with autograd."""
         with torch.no_grad():
             taps = self.feature_extractor(image)
-            scores = self.bank.scores(taps[self.bank.layer])
+            scores = self.bank.scores(taps[self.bank.layer], grouped=self.batched_scores)
             taps = {k: v.clone() for k, v in taps.items()}        # (the extractor may reuse its output buffers)
         with torch.enable_grad():
             if self.refiner_backend == 'hip':

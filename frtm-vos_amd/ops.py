@@ -130,6 +130,39 @@ def filter_scores(X, f, out=None, accumulate=False, n=None, interleave=None):
     return out
 
 
+def pointer_table(tensors, device):
+    """Device int64 table of the tensors' addresses (the w1T / w2 tables of target_apply_grouped), uploaded through pinned memory.
+    The caller keeps the tensors alive and rebuilds the table when one of them moves."""
+    return H.upload(torch.tensor([t.data_ptr() for t in tensors], dtype=torch.int64), device)
+
+
+def target_apply_grouped(feats, frame_of_pair, w1T_table, w2_table, c, cft=None, scores=None):
+    """Grouped target-model scoring (frtm_target_apply_grouped): for G (frame, target) pairs what G calls of
+    Discriminator.apply_window on one frame each compute, in two launches.
+    feats (F,Cin,h,w), frames dense inside but any pitch between them (a slice of a larger batch); frame_of_pair device int32 (G);
+    w1T_table / w2_table device int64 (G) addresses of the [Cin][c] projections / (1,c,3,3) filters (pointer_table).
+    Returns (cft (G,c,h,w), scores (G,1,h,w)); both may be given (dense, reused workspaces).  Raises on a shape the kernels refuse."""
+    if feats.dim() != 4 or feats.dtype != torch.float32 or not feats.is_cuda:
+        raise ValueError('target_apply_grouped: feats must be a (F,Cin,h,w) float32 tensor on the GPU (no CPU fallback)')
+    F_, Cin, h, w = feats.shape
+    if not feats[0].is_contiguous() or (F_ > 1 and feats.stride(0) < Cin * h * w):
+        raise ValueError('target_apply_grouped: every frame of feats must be dense')
+    G = frame_of_pair.numel()
+    for name, t, dt in (('frame_of_pair', frame_of_pair, torch.int32), ('w1T_table', w1T_table, torch.int64), ('w2_table', w2_table, torch.int64)):
+        if t.dtype != dt or t.device != feats.device or not t.is_contiguous() or t.numel() != G:
+            raise ValueError('target_apply_grouped: %s must be a dense %s tensor of %d entries on %s' % (name, dt, G, feats.device))
+    if cft is None:
+        cft = torch.empty(G, c, h, w, device=feats.device)
+    if scores is None:
+        scores = torch.empty(G, 1, h, w, device=feats.device)
+    if cft.numel() != G * c * h * w or scores.numel() != G * h * w or cft.dtype != torch.float32 or scores.dtype != torch.float32:
+        raise ValueError('target_apply_grouped: cft must hold (G,c,h,w) and scores (G,1,h,w) float32')
+    pitch = feats.stride(0) if F_ > 1 else Cin * h * w
+    H.call('frtm_target_apply_grouped', H.ptr(feats[0]), pitch, F_, H.ptr(frame_of_pair), H.ptr(w1T_table), H.ptr(w2_table),
+           G, Cin, int(c), h, w, H.ptr(cft), H.ptr(scores))
+    return cft, scores
+
+
 def transpose2d(x2d, out=None):
     rows, cols = x2d.shape
     if out is None:

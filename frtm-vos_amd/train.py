@@ -2,7 +2,7 @@
 
 ``python -m frtm_vos_amd.train NAME [--ftext resnet101|resnet18] [--dev cuda:0] [--dset synthetic|davis|ytvos|davis+ytvos]
 [--davis-path DIR] [--ytvos-path DIR] [--ytvos-sequences-file FILE] [--occlusion-overrides FILE] [--num-workers N] [--epochs N]
-[--batch-size B] [--workspace DIR]``
+[--batch-size B] [--workspace DIR] [--batched-scores]``
 
 Per batch: target models fitted on the augmented first frames on the HIP path (or read from the cache under the workspace), the
 refiner's forward and backward (``refiner_backend='hip'``), the loss tail (``loss_backend='hip'``) and the AMSGrad step (``FusedAdam``)
@@ -27,8 +27,9 @@ class ModelParameters:
     without pixel weighting, the 64-channel refiner with BatchNorm."""
 
     def __init__(self, name, feature_extractor='resnet101', device='cuda:0', batch_size=None, tmodel_cache_path=None, trunk_precision='fp32',
-                 refiner_precision='fp32'):
+                 refiner_precision='fp32', batched_scores=False):
         self.name, self.device, self.batch_size = name, device, batch_size
+        self.batched_scores = bool(batched_scores)    # the batch's target models score their frames in one grouped launch (TrainerModel.batched_scores)
         if trunk_precision not in ('fp32', 'bf16x3', 'bf16x1'):
             raise ValueError("trunk_precision must be 'fp32', 'bf16x3' or 'bf16x1', got %r" % (trunk_precision,))
         self.trunk_precision = trunk_precision        # the frozen trunk's routed 1x1 convs on bf16 pieces (ResnetFeatureExtractor.precision)
@@ -68,7 +69,7 @@ class ModelParameters:
         torch.manual_seed(1)                                       # seeded default init, as evaluate.Parameters.make_refiner
         refiner = SegNetwork(1, p.nchannels, chans, p.use_batch_norm, train_precision=self.refiner_precision).to(self.device)
         return TrainerModel(augmenter, extractor, self.disc_params, refiner, batch_size=self.batch_size, tmodel_cache=self.tmodel_cache,
-                            device=self.device, refiner_backend='hip', loss_backend='hip')
+                            device=self.device, refiner_backend='hip', loss_backend='hip', batched_scores=self.batched_scores)
 
 
 def parse_args(argv=None):
@@ -92,6 +93,9 @@ def parse_args(argv=None):
     ap.add_argument('--refiner-precision', choices=['fp32', 'bf16x1'], default='fp32',
                     help="the refiner's training pass: bf16x1 runs the routed 3x3 convs, input and weight gradients on bf16 MFMAs with fp32 "
                          "accumulation (NOT fp32-level; master weights, BatchNorm, 1x1 convs and checkpoints stay fp32)")
+    ap.add_argument('--batched-scores', action='store_true',
+                    help='score the frames of a batch with all its target models in one grouped launch (ops.target_apply_grouped) instead of one '
+                         'projection + filter pass per sample')
     return ap.parse_args(argv)
 
 
@@ -129,7 +133,8 @@ def main(argv=None):
         dataset = file_datasets(args, ws)
         hooks = dict(collate_fn=raw_collate, batch_transform=DeviceFrameResizer((480, 854), args.dev, datasets=dataset))
     params = ModelParameters(args.name, feature_extractor=args.ftext, device=args.dev, tmodel_cache_path=ws / 'tmodels_cache',
-                             batch_size=args.batch_size, trunk_precision=args.trunk_precision, refiner_precision=args.refiner_precision)
+                             batch_size=args.batch_size, trunk_precision=args.trunk_precision, refiner_precision=args.refiner_precision,
+                             batched_scores=args.batched_scores)
     model = params.get_model()
     optimizer = FusedAdam(model.refiner.parameters(), lr=1e-3, betas=(0.9, 0.999), weight_decay=1e-5, amsgrad=True)
     scheduler = torch.optim.lr_scheduler.StepLR(optimizer, step_size=127, gamma=0.1)

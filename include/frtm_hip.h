@@ -461,6 +461,17 @@ int frtm_track_merge(const float* logits, int frames, int n_obj, int HW, float* 
 /* frtm_filter_scores with a pitch (floats) between the output maps of consecutive samples (>= h*w). */
 int frtm_filter_scores_pitched(const float* X, const float* f, int N, int C, int h, int w, float* out, int out_pitch, int accumulate,
                                frtm_stream_t stream);
+/* Grouped target-model scoring (csrc/target_apply_grouped.hip): for G (frame, target) pairs, what G calls of frtm_conv2d (1x1 projection)
+ * + frtm_filter_scores on one frame each compute, in two launches.
+ *   feats          base of a feature batch (F, Cin, h, w); frame_pitch floats between frames (>= Cin*h*w: the frames need not be dense)
+ *   frame_of_pair  device int32[G]: the frame pair p reads; several pairs may name one frame (a pair naming none of the F frames is skipped)
+ *   w1T, w2        device tables of G pointers: projection in GEMM layout [Cin][c]; filter (1, c, 3, 3)
+ *   cft            (G, c, h, w) dense: pair p's projected features;   scores (G, 1, h, w) dense, in pair order
+ * Projection on fp32 MFMA, no split-K, no atomics: every element is one chain over K = Cin in ascending order; the 3x3 pass (zero
+ * padding) has one fixed summation order.  A pair's result does not depend on G, its place in the tables or the other pairs.
+ * Any h, w; c <= 128; Cin a multiple of 32; everything else fails with FRTM_ERR_ARG. */
+int frtm_target_apply_grouped(const float* feats, size_t frame_pitch, int F, const int* frame_of_pair, const float* const* w1T,
+                              const float* const* w2, int G, int Cin, int c, int h, int w, float* cft, float* scores, frtm_stream_t stream);
 /* count[k] = #pixels with masks[k] > 0.5   (the early-out test of discriminator.py:214), int32[n] */
 int frtm_count_above(const float* masks, int n, int HW, float thr, int* count, frtm_stream_t stream);
 
