@@ -666,11 +666,9 @@ class Discriminator(nn.Module):
     def apply(self, ft, interleave=None):
         """Per-frame scoring (reference :201-206).  ``interleave`` = (batch, k, groups): the score map is written into a caller's
         (frame, object) batch (ops.filter_scores) instead of a new tensor."""
-        H.require_gpu(ft, 'Discriminator.apply')
-        self.frame_num += 1
-        cft = ops.conv2d(ft.contiguous(), self._project_T(), self.project.out_channels, w_pitch=self.project.out_channels)
-        self.current_sample = cft
-        return ops.filter_scores(cft, self.filter.weight.data, interleave=interleave)
+        cft, scores = self.apply_window(ft, interleave=interleave)
+        self.advance(cft)
+        return scores
 
     def apply_window(self, ft, interleave=None):
         """Scores for a WINDOW of frames at once: ft (W,Cin,h,w) -> (projected features (W,c,h,w), scores (W,1,h,w)).  Pure:
@@ -812,3 +810,23 @@ class Discriminator(nn.Module):
             return
         opt.run(self.update_iters)
         self._solves_host += 1
+
+
+def apply_grouped(discs, feats, pairs_per_frame, cache, cft=None, scores=None):
+    """``Discriminator.apply`` for G target models in ONE launch pair (ops.target_apply_grouped): pair p is (frame p // pairs_per_frame of
+    ``feats``, discs[p]).  -> (cft (G,c,h,w), scores (G,1,h,w)); both may be given (dense workspaces the caller reuses).
+    ``cache``: a dict the caller keeps for this set of pairs; it holds the device pointer tables, which are rebuilt when a pointer or the
+    device changes -- a target model re-fitted, re-loaded or replaced by another one; a filter re-solve writes in place: no change."""
+    dev = feats.device
+    w1T = [d._project_T() for d in discs]
+    ptrs = [t.data_ptr() for t in w1T] + [d.filter.weight.data_ptr() for d in discs]
+    if cache.get('ptrs') != ptrs or cache.get('dev') != dev:
+        pairs = (len(discs), pairs_per_frame, dev)
+        if cache.get('pairs') != pairs:
+            cache.update(pairs=pairs, frames=H.upload(torch.arange(len(discs), dtype=torch.int32) // pairs_per_frame, dev))
+        cache.update(ptrs=ptrs, dev=dev, w1T=ops.pointer_table(w1T, dev), w2=ops.pointer_table([d.filter.weight.data for d in discs], dev))
+    cft, scores = ops.target_apply_grouped(feats, cache['frames'], cache['w1T'], cache['w2'], discs[0].project.out_channels,
+                                           cft=cft, scores=scores)
+    for p, d in enumerate(discs):
+        d.advance(cft[p:p + 1])
+    return cft, scores

@@ -5,7 +5,8 @@ the batch-1 trunk (2.1 ms for one frame, 0.9 ms per frame in a batch of 8).  A s
 batch-1 trunk: every stream delivers one frame per tick, so the frames of all streams share ONE trunk pass, and the streams with the same
 number of objects share one refiner pass and one merge (and, with ``grouped_apply``, one grouped target-model launch,
 ops.target_apply_grouped).  Each stream keeps its own target models and memory: per stream the arithmetic is that of ``track()``.  The
-reference has no such API.
+reference has no such API.  A group runs the step that ``track()`` and ``track_window()`` run: ``fused_step`` of
+model/tracker.py, with one list of target models per stream.
 
     pool = Parameters(weights).get_stream_pool(max_streams=8)
     sid = pool.open()
@@ -18,8 +19,7 @@ from collections import namedtuple
 import torch
 
 from .. import _hip as H
-from .. import ops
-from .tracker import FrameTaps, Tracker
+from .tracker import FrameTaps, Tracker, fused_step, persistent_taps
 
 TickBatch = namedtuple('TickBatch', 'size order groups fallbacks')
 TickPlan = namedtuple('TickPlan', 'batches skipped')
@@ -29,7 +29,7 @@ def plan_tick(entries):
     """The plan of one tick, a pure function of ``entries`` = (sid, frame size, number of active objects, eligible) per stream named.
 
     -> TickPlan(batches, skipped).  One TickBatch per frame size (sizes in ascending order): ``order`` = the sids in trunk-batch order,
-    ``groups`` = (start, g, n): the g streams order[start:start + g] have n active objects each and take the fused branch together --
+    ``groups`` = (start, g, n): the g streams order[start:start + g] have n active objects each and take the fused step together --
     contiguous in batch order, so their taps are one slice --, ``fallbacks`` = the batch indices of the streams that run their own
     ``track()`` on their slice of the taps (ineligible: an object starts on this frame, host-side guards, a raw log).  ``skipped`` =
     streams without an active object: they take no part in the tick.  The result does not depend on the order of ``entries``."""
@@ -92,7 +92,7 @@ class StreamPool:
         self._next_sid = 0
         self._disc_pool = []            # released target models, shared by all streams (Tracker.release_targets)
         self._bufs = {}                 # (kind, g, n, size) -> preallocated device tensor
-        self._tables = {}               # (g, n, size) -> pointer tables of the group that last ran under this key
+        self._tables = {}               # (g, n, size) -> apply_grouped's table cache of the group that last ran under this key
         self.grouped_launches = 0       # ops.target_apply_grouped calls so far (diagnostics)
 
     # ---- streams ------------------------------------------------------------------------------------------------------------
@@ -128,14 +128,8 @@ class StreamPool:
 
     # ---- one tick -----------------------------------------------------------------------------------------------------------
     def _eligible(self, tr, active):
-        """Would track() take its fused branch for this stream, with every early-out decided on the device?"""
-        n = len(active)
-        if not (tr.fuse_merge and active and n == len(tr.targets) and n < 16 and getattr(tr, '_raw_log', None) is None
-                and all(t.index == k + 1 for k, t in enumerate(active))):
-            return False
-        if not self.disc_params.update_filters:
-            return True
-        return all(t.discriminator.guards_on_device() for t in active)
+        """Does this stream's frame take the fused step (Tracker.fused_tail), with every early-out decided on the device?"""
+        return tr.fused_tail(active) and (not self.disc_params.update_filters or all(t.discriminator.guards_on_device() for t in active))
 
     def _buf(self, kind, key, shape, dtype=torch.float32):
         b = self._bufs.get((kind,) + key)
@@ -154,20 +148,13 @@ class StreamPool:
         entries, active_of = [], {}
         for sid, image in frames.items():
             tr = self._streams[sid].tracker
-            if getattr(tr, '_unchecked_fits', None):
+            if tr._unchecked_fits:
                 tr._check_first_frame_fits()            # as track(): no frame is scored with a half-fitted model
-            active = [t for t in tr.targets.values() if t.start_frame < tr.current_frame]
-            active_of[sid] = active
+            active = active_of[sid] = tr.active_targets()
             entries.append((sid, tuple(image.shape[-2:]), len(active), self._eligible(tr, active)))
         plan = plan_tick(entries)
         out = {}
         ext = self.feature_extractor
-        persistent = hasattr(ext, 'reuse_outputs')
-        if persistent:
-            saved = (ext.reuse_outputs, ext.use_graph, ext.output_set)
-            ext.reuse_outputs, ext.use_graph, ext.output_set = True, False, 0
-            if ext.lanes != max(1, self.trunk_lanes):
-                ext.lanes = max(1, self.trunk_lanes)
         for tb in plan.batches:
             for k in tb.fallbacks:
                 st = self._streams[tb.order[k]]
@@ -175,7 +162,7 @@ class StreamPool:
                     # its mask stack is a row of a merge buffer that a group of this tick may write; track() works in place: on a copy
                     st.tracker.current_masks = st.tracker.current_masks.clone()
                     st.pool_masks = False
-        try:
+        with persistent_taps(ext, max(1, self.trunk_lanes), False, [(ext, 'output_set', 0)]):
             for tb in plan.batches:
                 B = len(tb.order)
                 batch = self._buf('frames', (B, 3, tb.size), (B, 3) + tb.size, torch.uint8)
@@ -188,55 +175,29 @@ class StreamPool:
                     sid = tb.order[k]
                     out[sid] = self._streams[sid].tracker.track(batch[k], features=FrameTaps(taps, k))
                 del taps                                                # no tap view outlives the tick: the next pass overwrites them
-        finally:
-            if persistent:
-                ext.reuse_outputs, ext.use_graph, ext.output_set = saved
         for sid in frames:
             self._streams[sid].tracker.current_frame += 1
         return out
 
     def _run_group(self, tb, start, g, n, taps, active_of, out):
-        """The fused branch of track() for g streams of n objects at once: pair p = i * n + k is (stream i of the group, its object k)."""
+        """The fused step (model/tracker.py: fused_step) for g streams of n objects at once, one frame each, on the pool's buffers:
+        pair p = i * n + k is (stream i of the group, its object k)."""
         key = (g, n, tb.size)
         sids = tb.order[start:start + g]
-        discs = [t.discriminator for sid in sids for t in active_of[sid]]
-        layer = active_of[sids[0]][0].disc_layer
+        first = active_of[sids[0]][0]
         feats = {L: t[start:start + g] for L, t in taps.items()}
-        ft = feats[layer]
-        h_, w_ = ft.shape[-2:]
+        h_, w_ = feats[first.disc_layer].shape[-2:]
         P = g * n
-        c = discs[0].project.out_channels
-        scores = self._buf('scores', key, (P, 1, h_, w_))
+        grouped = None
         if self.grouped_apply and P >= self.min_pairs:
-            w1T = [d._project_T() for d in discs]
-            ptrs = [t.data_ptr() for t in w1T] + [d.filter.weight.data_ptr() for d in discs]
-            tab = self._tables.get(key)
-            if tab is None or tab['ptrs'] != ptrs:
-                # membership of the group or one of the pointers changed (a filter re-solve writes in place: no change)
-                tab = self._tables[key] = dict(ptrs=ptrs, w1T=ops.pointer_table(w1T, self.device),
-                                               w2=ops.pointer_table([d.filter.weight.data for d in discs], self.device),
-                                               frames=tab['frames'] if tab is not None else
-                                               H.upload(torch.arange(P, dtype=torch.int32) // n, self.device))
-            cft = self._buf('cft', key, (P, c, h_, w_))
-            ops.target_apply_grouped(ft, tab['frames'], tab['w1T'], tab['w2'], c, cft=cft, scores=scores)
+            grouped = (self._tables.setdefault(key, {}), self._buf('cft', key, (P, first.discriminator.project.out_channels, h_, w_)))
             self.grouped_launches += 1
-            for p, d in enumerate(discs):
-                d.advance(cft[p:p + 1])
-        else:
-            for p, d in enumerate(discs):
-                d.apply(ft[p // n:p // n + 1], interleave=(scores, p, P))
-        size = tb.size
-        logits = self.refiner(scores, feats, size)                      # (g * n, 1, H, W), frame-major
-        masks = self._buf('masks', key, (g, n + 1) + size)
         update = bool(self.disc_params.update_filters)
-        counts = self._buf('counts', key, (g, n + 1), torch.int32) if update else None
-        ops.track_merge(logits, g, n, masks, None, None, False, counts)
+        masks, _ = fused_step(self.refiner, [active_of[sid] for sid in sids], feats, tb.size, update,
+                              scores=self._buf('scores', key, (P, 1, h_, w_)), masks=self._buf('masks', key, (g, n + 1) + tb.size),
+                              counts=self._buf('counts', key, (g, n + 1), torch.int32) if update else None, grouped=grouped)
         for i, sid in enumerate(sids):
             st = self._streams[sid]
-            if update:
-                for t in active_of[sid]:
-                    y = masks[i, t.index].unsqueeze(0).unsqueeze(0)
-                    t.discriminator.update(y, count_dev=counts[i, t.index:t.index + 1])
             st.tracker.current_masks = masks[i]
             st.pool_masks = True
             out[sid] = masks[i]

@@ -19,6 +19,7 @@ per-object memory/filter update -- with the device work re-laid out for one MI35
    one kernel; on frames without a filter re-solve it guards the memory insert on the device (no host sync at all), on
    re-solve frames (every 8th) ONE small device->host copy serves all objects.
 """
+from contextlib import contextmanager
 from time import time
 
 import numpy as np
@@ -30,7 +31,7 @@ import torch.nn.functional as F
 from .. import ops
 from .. import _hip as H
 from ..lib.utils import AverageMeter
-from .discriminator import Discriminator
+from .discriminator import Discriminator, apply_grouped
 
 
 _STREAMS = {}
@@ -104,6 +105,95 @@ def _independent_stream(device, role, others, tries=6):
     STREAM_PROBE[role] = dict(probed=probe, independent=found)
     return _STREAMS[key]
 
+
+@contextmanager
+def persistent_taps(ext, lanes, use_graph, also=()):
+    """The trunk ``ext`` writes its taps into persistent buffers for the duration, ``lanes`` sub-batches at a time, replayed as hipGraphs
+    or not; ``also``: further (object, attribute, value) settings for the duration.  Everything but the lane count is put back afterwards:
+    a caller that holds two results of ext() (no_grad_forward's chunks, user code) must not find them aliased.  Yields whether the taps
+    are persistent; a caller-supplied extractor without ``reuse_outputs`` is left alone."""
+    if not hasattr(ext, 'reuse_outputs'):
+        yield False
+        return
+    settings = [(ext, 'reuse_outputs', True), (ext, 'use_graph', use_graph)] + list(also)
+    saved = [(o, a, getattr(o, a)) for o, a, _ in settings]
+    for o, a, v in settings:
+        setattr(o, a, v)
+    if ext.lanes != lanes:
+        ext.lanes = lanes
+    try:
+        yield True
+    finally:
+        for o, a, v in saved:
+            setattr(o, a, v)
+
+
+def update_targets(active, cfts, masks, counts, update_filters, windowed):
+    """Memory inserts and filter re-solves after W tracked frames, frame by frame in order.  ``masks`` (W,n_obj+1,H,W) merged,
+    ``cfts[k]`` (W,c,h,w) projected features of active[k] -- None: the scoring has advanced the target models itself (apply_grouped) --,
+    ``counts`` (W,n_obj+1) device int32 pixels per plane, or None: counted here.  ``windowed``: one batched update per object
+    (Discriminator.update_window) when every insert and the re-solve at the end are decided on the device."""
+    W, K = masks.shape[:2]
+
+    def advance(f):
+        for k, t in enumerate(active if cfts is not None else ()):
+            t.discriminator.advance(cfts[k] if W == 1 else cfts[k][f:f + 1])
+
+    def on_device():
+        return all(t.discriminator.guards_on_device() for t in active)
+    if not (active and update_filters):
+        for f in range(W):
+            advance(f)
+        return
+    if counts is None:
+        counts = ops.count_above(masks.reshape(W * K, *masks.shape[-2:])).view(W, K)     # device int32, no sync
+    if windowed and on_device() and masks.is_contiguous() and all(t.discriminator.can_update_window(W) for t in active):
+        for k, t in enumerate(active):
+            t.discriminator.update_window(cfts[k], masks, t.index, counts)
+        return
+    flat = counts.view(-1)
+    for f in range(W):
+        advance(f)
+        solve = any(t.discriminator.frame_num % t.discriminator.train_skipping == 0 for t in active)
+        host = counts[f].tolist() if solve and not on_device() else None                 # (no D2H at all when the early-out runs on the device)
+        for t in active:
+            i = t.index                                                                  # (one view each: (1,1,H,W) plane, (1,) count)
+            t.discriminator.update(masks[f:f + 1, i:i + 1], num_positive=None if host is None else host[i], count_dev=flat[f * K + i:f * K + i + 1])
+
+
+def fused_step(refiner, frame_targets, feats, size, update_filters, windowed=False, scores=None, masks=None, counts=None,
+               lut=None, single=False, grouped=None):
+    """The tracking step of F frames of n objects each when every mask plane comes from the refiner (Tracker.fused_tail): scores into
+    one frame-major batch, refiner, then sigmoid + merge + pixel counts + label decoding as ONE kernel (ops.track_merge), then
+    update_targets.  ``frame_targets[f]``: the n TargetObjects of frame f; consecutive frames that share a list are scored as one
+    window.  track(): F = 1; track_window(): W frames, one list; a StreamPool group: one list per stream.  ``scores`` / ``masks`` /
+    ``counts``: the caller's buffers (else allocated); ``lut``: labels are decoded through it; ``grouped`` = (table cache, cft workspace):
+    one grouped launch scores all pairs (apply_grouped; every frame has its own list).  -> (masks (F,n+1,H,W), labels (F,1,H,W) or None)."""
+    F_, n = len(frame_targets), len(frame_targets[0])
+    ft = feats[frame_targets[0][0].disc_layer]
+    dev = ft.device
+    if scores is None:
+        scores = torch.empty(F_ * n, 1, *ft.shape[-2:], device=dev)
+    cuts = [f for f in range(F_) if f == 0 or frame_targets[f] is not frame_targets[f - 1]] + [F_]
+    runs = list(zip(cuts[:-1], cuts[1:]))
+    part = (lambda t, a, b: t) if len(runs) == 1 else (lambda t, a, b: t[a:b])           # (no view of the whole: track() is bound by the host)
+    if grouped is not None:
+        apply_grouped([t.discriminator for ts in frame_targets for t in ts], ft, n, grouped[0], cft=grouped[1], scores=scores)
+        cfts = [None] * F_
+    else:
+        cfts = [[t.discriminator.apply_window(part(feats[t.disc_layer], f0, f1), interleave=(part(scores, f0 * n, f1 * n), k, n))[0]
+                 for k, t in enumerate(frame_targets[f0])] for f0, f1 in runs]
+    logits = refiner(scores, feats, size)                                                # (F*n,1,H,W), frame-major
+    if masks is None:
+        masks = torch.empty(F_, n + 1, *size, device=dev)
+    labels = torch.empty(F_, 1, *size, dtype=torch.uint8, device=dev) if lut is not None else None
+    if counts is None and update_filters:
+        counts = torch.empty(F_, n + 1, dtype=torch.int32, device=dev)
+    ops.track_merge(logits, F_, n, masks, labels, lut, single, counts)
+    masks = masks.view(F_, n + 1, *size)
+    for (f0, f1), cft in zip(runs, cfts):
+        update_targets(frame_targets[f0], cft, part(masks, f0, f1), None if counts is None else part(counts, f0, f1), update_filters, windowed)
+    return masks, labels
 
 
 class FrameTaps(dict):
@@ -213,6 +303,11 @@ class Tracker(nn.Module):
         self._single = False
         self._window_labels = None
         self._raw_log = None             # list: (frame, masks before the merge) of every tracked frame is appended (ytvos merge, parity tests)
+        self._unchecked_fits = []        # targets whose first-frame fit has not been asked for a timed-out resident launch yet
+        self._in_run_sequence = False    # run_sequence asks after the sequence (_check_first_frame_fits), track() before the frame
+        self._rerun = False              # the sequence is being tracked again after a resident launch timed out
+        self.object_ids = None
+        self.last_enqueue_seconds = 0.0
 
     def release_targets(self):
         """Ends a sequence: the target models go back to a pool and serve the next sequence's objects, so that the steady
@@ -455,7 +550,7 @@ class Tracker(nn.Module):
         if any(late):
             torch.cuda.synchronize()
         missing = [d.init_aborted() for d in discs]
-        if (any(missing) or any(late) or any(d.num_persistent_aborts > 0 for d in discs)) and not getattr(self, '_rerun', False):
+        if (any(missing) or any(late) or any(d.num_persistent_aborts > 0 for d in discs)) and not self._rerun:
             from .discriminator import DiscriminatorLoss
             from .optimizer import GaussNewtonCG
             DiscriminatorLoss.persistent_joint = False
@@ -497,7 +592,7 @@ class Tracker(nn.Module):
     def _window_complete(self, length, image):
         """A window ends with the frame on which some object re-solves its filter (the frames before it all see the same filter,
         reference discriminator.py:221-227), or when it holds as many samples as the refiner's 32-bit buffer offsets allow."""
-        active = [t for t in self.targets.values() if t.start_frame < self.current_frame]
+        active = self.active_targets()
         if not self.window_tracking or not active:
             return True
         if any(t.discriminator.frames_until_solve() <= length for t in active if t.discriminator.update_filters):
@@ -517,24 +612,9 @@ class Tracker(nn.Module):
         frames = list(sequence)
         fb = max(1, int(self.feature_batch))
         ext = self.feature_extractor
-        persistent = hasattr(ext, 'reuse_outputs')
-        saved = None
-        if persistent:
-            # persistent taps / graph replay only for the duration of this sequence: a caller that holds two results of ext()
-            # (no_grad_forward's chunks, user code) must not find them aliased afterwards
-            saved = (ext.reuse_outputs, ext.use_graph, getattr(self.refiner, 'use_graphs', None))
-            ext.reuse_outputs = True
-            ext.lanes = max(1, min(int(self.trunk_lanes), fb))
-            ext.use_graph = self.graph_trunk
-            if hasattr(self.refiner, 'use_graphs'):
-                self.refiner.use_graphs = self.graph_refiner
-        try:
+        also = [(self.refiner, 'use_graphs', self.graph_refiner)] if hasattr(self.refiner, 'use_graphs') else []
+        with persistent_taps(ext, max(1, min(int(self.trunk_lanes), fb)), self.graph_trunk, also) as persistent:
             yield from self._frames_with_features(frames, fb, ext, persistent)
-        finally:
-            if saved is not None:
-                ext.reuse_outputs, ext.use_graph = saved[0], saved[1]
-                if saved[2] is not None:
-                    self.refiner.use_graphs = saved[2]
 
     def _frame_batch(self, ims):
         """(B,3,H,W) uint8 batch of consecutive frames for the trunk.  Sequences pre-load their frames as slices of ONE device tensor
@@ -561,7 +641,7 @@ class Tracker(nn.Module):
         if k == 1 or not self.balance_batches:
             sizes = [min(fb, n - i) for i in range(0, n, fb)]
             # a tail of a few frames does not fill the GPU (3 frames: 77 TFLOP/s against 113 for 16): it joins the pass before it
-            if len(sizes) > 1 and sizes[-1] <= int(getattr(self, 'fold_tail', 0)):
+            if len(sizes) > 1 and sizes[-1] <= int(self.fold_tail):
                 sizes[-2:] = [sizes[-2] + sizes[-1]]
             return sizes
         q = max(1, int(getattr(self.disc_params, 'train_skipping', 8)))
@@ -728,7 +808,7 @@ class Tracker(nn.Module):
             share = self.share_first_sample and len(fresh) > 1
             # (opt-in, concurrent_init_pass: with the first tracking pass in flight on a side stream this pass takes the trunk's SECOND lane
             # set and runs next to it instead of behind it; measured: no gain, see __init__)
-            early = getattr(self, '_early_pass_event', None) if self.concurrent_init_pass else None
+            early = self._early_pass_event if self.concurrent_init_pass else None
             kw = dict(lane_set=1) if early is not None else {}      # (a caller-supplied extractor need not know about lane sets)
             def gather(parts):                  # (torch.cat without its framework kernel: device-to-device copies into one batch)
                 out = torch.empty((sum(p.shape[0] for p in parts),) + tuple(parts[0].shape[1:]), dtype=parts[0].dtype, device=parts[0].device)
@@ -787,7 +867,7 @@ class Tracker(nn.Module):
                 b0 += k
             for st in lanes:
                 cur.wait_stream(st)
-            self._unchecked_fits = getattr(self, '_unchecked_fits', []) + [t for t, _, _ in fresh]
+            self._unchecked_fits = self._unchecked_fits + [t for t, _, _ in fresh]
         return self.current_masks
 
     def _check_first_frame_fits(self):
@@ -801,82 +881,60 @@ class Tracker(nn.Module):
             if d is not None and self.targets.get(t.object_id) is t and d.init_aborted():
                 d.refit_in_chain_form()
 
+    def active_targets(self):
+        """The objects tracked on the current frame: those that started before it."""
+        return [t for t in self.targets.values() if t.start_frame < self.current_frame]
+
+    def fused_tail(self, active):
+        """Does every plane of the mask stack come from the refiner (no object starts on this frame, no raw masks are being logged)?  Then
+        the tail of the step is ONE kernel (fused_step); otherwise the step-by-step form (_track_stepwise)."""
+        n = len(active)
+        return bool(self.fuse_merge and active and n == len(self.targets) and n < 16 and self._raw_log is None
+                    and all(t.index == k + 1 for k, t in enumerate(active)))
+
+    def _track_stepwise(self, active, feats, size, W, windowed):
+        """The tracking step of W frames in the reference's steps (tracker.py:198-221), on W copies of ``current_masks``."""
+        masks = self.current_masks.unsqueeze(0).repeat(W, 1, 1, 1) if W > 1 else self.current_masks.unsqueeze(0)
+        cfts = []
+        if active:
+            n = len(active)
+            per_obj = [t.discriminator.apply_window(feats[t.disc_layer]) for t in active]          # (W,c,h,w), (W,1,h,w)
+            cfts = [c for c, _ in per_obj]
+            scores = torch.stack([s for _, s in per_obj], dim=1).reshape(W * n, 1, *per_obj[0][1].shape[-2:])   # frame-major
+            y = torch.sigmoid(self.refiner(scores, feats, size)).view(W, n, *size)
+            for k, t in enumerate(active):
+                masks[:, t.index] = y[:, k]
+        for t1 in active:                                                                        # :208-212 (only when W == 1)
+            for t2 in self.targets.values():
+                if t2 is not t1 and t2.start_frame == self.current_frame:
+                    masks[0, t1.index] *= (1 - t2.start_mask.squeeze(0)).float()
+        if self._raw_log is not None:
+            for f in range(W):
+                self._raw_log.append((self.current_frame + f, masks[f].clone()))
+        ops.merge_masks_(masks)                                                                  # :214-221, all frames of the window
+        update_targets(active, cfts, masks, None, self.disc_params.update_filters, windowed)
+        return masks
+
     @torch.no_grad()
     @H.roctx('track_window')
     def track_window(self, images, taps):
         """track() for W consecutive frames at once (one contiguous slice of a trunk batch, same active objects, no filter
         re-solve before the last frame): one projection / score / refiner pass over W x n samples instead of W passes over n.
-        Per frame the arithmetic is that of track(); the memory inserts and the re-solve run frame by frame afterwards, in order.
+        Per frame the arithmetic is that of track(); the memory inserts and the re-solve run frame by frame afterwards, in order
+        (as one batched update per object when that is decided on the device).
         Returns the per-frame ``current_masks`` stacked: (W, n_obj+1, H, W)."""
         W = len(images)
         im_size = images[0].shape[-2:]
         first = taps[0]
-        if W > 1 or isinstance(first, FrameTaps):
-            feats = {L: first.batch[L][first.k:first.k + W] for L in first.batch} if isinstance(first, FrameTaps) else first
-        else:
-            feats = first
-        active = [t for t in self.targets.values() if t.start_frame < self.current_frame]
-        n = len(active)
+        feats = {L: first.batch[L][first.k:first.k + W] for L in first.batch} if isinstance(first, FrameTaps) else first
+        active = self.active_targets()
         self._window_labels = None
-        cfts, counts = [], None
-        # Every plane comes from the refiner (no object starts on these frames) -> the whole tail of track() is ONE kernel: sigmoid,
-        # merge, pixel counts and label decoding (ops.track_merge); the score maps are written straight into the refiner's
-        # (frame, object) batch.  Otherwise (an object starts here / raw masks are being logged): the step-by-step form below.
-        fused = bool(self.fuse_merge and active and n == len(self.targets) and n < 16 and getattr(self, '_raw_log', None) is None
-                     and all(t.index == k + 1 for k, t in enumerate(active)))
-        if fused:
-            h_, w_ = feats[active[0].disc_layer].shape[-2:]
-            scores = torch.empty(W * n, 1, h_, w_, device=self.device)
-            cfts = [t.discriminator.apply_window(feats[t.disc_layer], interleave=(scores, k, n))[0] for k, t in enumerate(active)]
-            logits = self.refiner(scores, feats, im_size)                                        # (W*n,1,H,W), frame-major
-            masks = torch.empty(W, n + 1, *im_size, device=self.device)
-            labels = torch.empty(W, 1, *im_size, dtype=torch.uint8, device=self.device) if self._lut is not None else None
-            counts = torch.empty(W, n + 1, dtype=torch.int32, device=self.device) if self.disc_params.update_filters else None
-            ops.track_merge(logits, W, n, masks, labels, self._lut, self._single, counts)
-            self._window_labels = labels
+        if self.fused_tail(active):
+            # (the score maps are written straight into the refiner's (frame, object) batch; the merge kernel decodes the labels on the way)
+            masks, self._window_labels = fused_step(self.refiner, [active] * W, feats, im_size, self.disc_params.update_filters,
+                                                    windowed=True, lut=self._lut, single=self._single)
         else:
-            masks = self.current_masks.unsqueeze(0).repeat(W, 1, 1, 1) if W > 1 else self.current_masks.unsqueeze(0)
-            if active:
-                per_obj = [t.discriminator.apply_window(feats[t.disc_layer]) for t in active]      # (W,c,h,w), (W,1,h,w)
-                cfts = [c for c, _ in per_obj]
-                scores = torch.stack([s for _, s in per_obj], dim=1).reshape(W * n, 1, *per_obj[0][1].shape[-2:])   # frame-major
-                y = torch.sigmoid(self.refiner(scores, feats, im_size)).view(W, n, *im_size)
-                for k, t in enumerate(active):
-                    masks[:, t.index] = y[:, k]
-            for t1 in active:                                                                    # :208-212 (only when W == 1)
-                for t2 in self.targets.values():
-                    if t2 is not t1 and t2.start_frame == self.current_frame:
-                        masks[0, t1.index] *= (1 - t2.start_mask.squeeze(0)).float()
-            if getattr(self, '_raw_log', None) is not None:
-                for f in range(W):
-                    self._raw_log.append((self.current_frame + f, masks[f].clone()))
-            ops.merge_masks_(masks)                                                              # :214-221, all frames of the window
-        if active and self.disc_params.update_filters:
-            K = masks.shape[1]
-            if counts is None:
-                counts = ops.count_above(masks.view(W * K, *im_size)).view(W, K)             # device int32, no sync
-            on_device = all(t.discriminator.guards_on_device() for t in active)
-            if on_device and masks.is_contiguous() and all(t.discriminator.can_update_window(W) for t in active):
-                # every insert of the window and the re-solve at its end decided on the device: one batched update per object
-                for k, t in enumerate(active):
-                    t.discriminator.update_window(cfts[k], masks, t.index, counts)
-                self.current_masks = masks[W - 1]
-                return masks
-            for f in range(W):
-                for t in active:
-                    t.discriminator.advance(cfts[active.index(t)][f:f + 1])
-                solve = any(t.discriminator.frame_num % t.discriminator.train_skipping == 0 for t in active)
-                host = counts[f].tolist() if solve and not on_device else None               # (no D2H at all when the early-out runs on the device)
-                for t in active:
-                    y1 = masks[f, t.index].unsqueeze(0).unsqueeze(0)
-                    if host is not None:
-                        t.discriminator.update(y1, num_positive=host[t.index], count_dev=counts[f, t.index:t.index + 1])
-                    else:
-                        t.discriminator.update(y1, count_dev=counts[f, t.index:t.index + 1])
-        else:
-            for f in range(W):
-                for k, t in enumerate(active):
-                    t.discriminator.advance(cfts[k][f:f + 1])
+            masks = self._track_stepwise(active, feats, im_size, W, windowed=True)
         self.current_masks = masks[W - 1]
         return masks
 
@@ -884,47 +942,13 @@ class Tracker(nn.Module):
     def track(self, image, features=None):
         """Reference tracker.py:193-227.  ``features``: optional pre-computed taps of this frame (frames_with_features)."""
         im_size = image.shape[-2:]
-        if getattr(self, '_unchecked_fits', None) and not getattr(self, '_in_run_sequence', False):
+        if self._unchecked_fits and not self._in_run_sequence:
             self._check_first_frame_fits()
         if features is None:
             features = self.feature_extractor(image)
-        active = [t for t in self.targets.values() if t.start_frame < self.current_frame]
-        n = len(active)
-        counts = None
-        fused = bool(self.fuse_merge and active and n == len(self.targets) and n < 16 and getattr(self, '_raw_log', None) is None
-                     and all(t.index == k + 1 for k, t in enumerate(active)) and self.current_masks.is_contiguous())
-        if fused:
-            # all planes come from the refiner: scores into one batch, then sigmoid + merge + pixel counts as one kernel (ops.track_merge)
-            h_, w_ = features[active[0].disc_layer].shape[-2:]
-            scores = torch.empty(n, 1, h_, w_, device=self.device)
-            for k, t in enumerate(active):
-                t.classify(features[t.disc_layer], interleave=(scores, k, n))
-            logits = self.refiner(scores, features, im_size)
-            counts = torch.empty(1, n + 1, dtype=torch.int32, device=self.device) if self.disc_params.update_filters else None
-            ops.track_merge(logits, 1, n, self.current_masks, None, None, False, counts)
-            counts = None if counts is None else counts[0]
+        active = self.active_targets()
+        if self.fused_tail(active) and self.current_masks.is_contiguous():
+            fused_step(self.refiner, [active], features, im_size, self.disc_params.update_filters, masks=self.current_masks)    # in place
         else:
-            if active:
-                scores = torch.cat([t.classify(features[t.disc_layer]) for t in active])       # (n,1,h,w)
-                y = torch.sigmoid(self.refiner(scores, features, im_size))                       # (n,1,H,W)
-                for k, t in enumerate(active):
-                    self.current_masks[t.index] = y[k, 0]
-            for t1 in active:                                                                    # :208-212
-                for t2 in self.targets.values():
-                    if t2 is not t1 and t2.start_frame == self.current_frame:
-                        self.current_masks[t1.index] *= (1 - t2.start_mask.squeeze(0)).float()
-            if getattr(self, '_raw_log', None) is not None:
-                self._raw_log.append((self.current_frame, self.current_masks.clone()))
-            ops.merge_masks_(self.current_masks)                                                 # :214-221
-        if active and self.disc_params.update_filters:
-            if counts is None:
-                counts = ops.count_above(self.current_masks)                                 # device int32 (n_obj+1), no sync
-            solve = any(t.discriminator.frame_num % t.discriminator.train_skipping == 0 for t in active)
-            host = counts.tolist() if solve and not all(t.discriminator.guards_on_device() for t in active) else None
-            for k, t in enumerate(active):
-                y = self.current_masks[t.index].unsqueeze(0).unsqueeze(0)
-                if host is not None:
-                    t.discriminator.update(y, num_positive=host[t.index])
-                else:
-                    t.discriminator.update(y, count_dev=counts[t.index:t.index + 1])
+            self._track_stepwise(active, features, im_size, 1, windowed=False)
         return self.current_masks

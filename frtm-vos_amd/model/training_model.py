@@ -27,7 +27,7 @@ import torch.nn as nn
 
 from .. import _hip as H
 from ..lib.utils import interpolate
-from .discriminator import Discriminator
+from .discriminator import Discriminator, apply_grouped
 from .train_loss import bce_logits_stats, iou_from_counts
 
 
@@ -129,33 +129,21 @@ class TargetModelBank:
     @torch.no_grad()
     def scores(self, layer_features, grouped=False):
         """(B,Cin,h,w) -> (B,1,h,w): sample i scored by target model i.  ``grouped``: one ops.target_apply_grouped call over the B
-        pairs (frame i, slot i) instead of B times Discriminator.apply (three small launches each)."""
+        pairs (frame i, slot i), discriminator.apply_grouped, instead of B times Discriminator.apply (three small launches each)."""
         if not grouped:
             return torch.cat([slot.discriminator.apply(layer_features[i:i + 1]) for i, slot in enumerate(self.slots[:layer_features.shape[0]])])
-        from .. import ops
         H.require_gpu(layer_features, 'TargetModelBank.scores')
         B = layer_features.shape[0]
         discs = [slot.discriminator for slot in self.slots[:B]]
-        dev = layer_features.device
-        c = discs[0].project.out_channels
-        ptrs = [d._project_T().data_ptr() for d in discs] + [d.filter.weight.data_ptr() for d in discs]
+        if self._grouped is None:
+            self._grouped = dict(tables={}, cft=None)
         g = self._grouped
-        if g is None or g['ptrs'] != ptrs or g['dev'] != dev:
-            # the tables change when a slot is re-fitted or re-loaded (its GEMM-layout projection is a new tensor), not per frame
-            g = self._grouped = dict(ptrs=ptrs, dev=dev, cft=None if g is None or g['dev'] != dev else g['cft'],
-                                     w1T=ops.pointer_table([d._project_T() for d in discs], dev),
-                                     w2=ops.pointer_table([d.filter.weight.data for d in discs], dev),
-                                     frames=H.upload(torch.arange(B, dtype=torch.int32), dev))
-        shape = (B, c) + tuple(layer_features.shape[-2:])
-        if g['cft'] is None or tuple(g['cft'].shape) != shape:
-            g['cft'] = torch.empty(shape, device=dev)                # reused workspace: the projected features are not kept in training
+        shape = (B, discs[0].project.out_channels) + tuple(layer_features.shape[-2:])
+        if g['cft'] is None or tuple(g['cft'].shape) != shape or g['cft'].device != layer_features.device:
+            g['cft'] = torch.empty(shape, device=layer_features.device)   # reused workspace: the projected features are not kept in training
         feats = layer_features if layer_features[0].is_contiguous() else layer_features.contiguous()
-        cft, scores = ops.target_apply_grouped(feats, g['frames'], g['w1T'], g['w2'], c, cft=g['cft'])
-        for i, d in enumerate(discs):                                 # the bookkeeping of Discriminator.apply
-            d.frame_num += 1
-            d.current_sample = cft[i:i + 1]
-        return scores
-
+        # (the tables change when a slot is re-fitted or re-loaded -- its GEMM-layout projection is a new tensor --, not per frame)
+        return apply_grouped(discs, feats, 1, g['tables'], cft=g['cft'])[1]
 
 def mask_iou(pred, gt):
     """IoU of the thresholded maps per sample; two empty masks count as a perfect match."""

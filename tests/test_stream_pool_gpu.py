@@ -239,6 +239,15 @@ def test_pool_with_per_pair_apply_matches_the_literal_loop(sequences, literal):
     _compare(soft, literal)
 
 
+def test_a_pool_of_one_stream_is_bitwise_the_literal_loop(sequences, literal):
+    """One stream is a group with g = 1 scored pair by pair: track()'s launches on track()'s shapes, through the same definition of
+    the tracking step (model/tracker.py: fused_step).  So no tolerance: the masks of every frame are the literal loop's, bit for bit."""
+    soft, fused = _pool_run(sequences[:1], False)
+    assert fused == 0 and sorted(soft[0]) == sorted(literal[0]) and len(literal[0]) >= 10
+    for t in literal[0]:
+        assert torch.equal(soft[0][t], literal[0][t]), t
+
+
 def test_two_pool_runs_are_bitwise_equal(sequences, grouped_run):
     """No race on the shared tap buffers, the merge buffers or the pointer tables: a second run gives the same masks on every frame."""
     again, _ = _pool_run(sequences, True)
