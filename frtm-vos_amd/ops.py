@@ -101,6 +101,13 @@ def conv2d(x, wT, Cout, ksize=1, stride=1, pad=0, ktab=None, scale=None, shift=N
     Wo = (Win + 2 * pad - ksize) // stride + 1
     if out is None:
         out = torch.empty((B, Ho * Wo, Cout) if out_transposed else (B, Cout, Ho, Wo), device=x.device, dtype=torch.float32)
+    if w_pitch > 0 and (w_pitch % 4 or wT.data_ptr() % 16):
+        # frtm_conv2d reads a plain [K][w_pitch] matrix in 16-byte pieces: a pitch that is no multiple of 4 (a target model whose c is
+        # none: the matrices of DiscriminatorLoss are dense (., c)) or a misaligned start goes through a zero-padded copy
+        K, pitch = Cin * ksize * ksize, (int(w_pitch) + 3) // 4 * 4
+        staged = torch.zeros(K, pitch, device=x.device, dtype=torch.float32)
+        staged[:, :w_pitch].copy_(wT.reshape(-1)[:K * w_pitch].view(K, w_pitch))
+        wT, w_pitch = staged, pitch
     out_elems = Cout * B * Ho * Wo
     # split-K only happens for small outputs (< ~800 workgroups); the library clamps the factor to the capacity given here
     # `ws`: the caller's own split-K scratch (hipGraphs that may replay concurrently must not share the per-stream one)
