@@ -14,6 +14,8 @@ but every tensor op is a hand-written gfx950 kernel reached through libfrtm_hip.
   init       joint problem over (project, filter): the two 1x1 GEMMs per operator application
              (forward conv and weight gradient) run on the MFMA conv kernel, K = Cin resp. K = 5*h*w.
 """
+import os
+
 import torch
 import torch.nn as nn
 
@@ -32,6 +34,14 @@ class DiscriminatorLoss(MinimizationProblem):
     joint=True:  variables [project.weight (c,Cin,1,1), filter.weight], data = raw backbone features.
     Flat vector layout used by the solver: [ project^T as (Cin,c) | filter as (c,9) ].
     """
+
+    wide_forms = not os.environ.get('FRTM_NO_WIDE')     # maps wider than a wavefront: the strip forms of csrc/wide_maps.hip
+    persistent_joint = not os.environ.get('FRTM_NO_PERSISTENT_JOINT')     # joint problem: a Gauss-Newton iteration as ONE resident launch (csrc/joint_persistent.hip)
+    # True: the projection part of the joint problem in its composed form (csrc/joint_fit.hip: k_joint_compose / k_joint_expand):
+    # the raw features are filtered with the composed 3x3 kernel p1 . w2 and their 3x3 weight gradient is expanded through w2 --
+    # two HBM-bound passes over the raw features per operator application instead of two Cin x c x pixels GEMMs.
+    composed = True
+    fused = True        # joint problem: merged glue kernels (csrc/joint_fit.hip), 8 instead of 13 launches per CG iteration
 
     def __init__(self, *args, **kwargs):
         """Two call forms:
@@ -145,8 +155,6 @@ class DiscriminatorLoss(MinimizationProblem):
         H.call('frtm_stencil', H.ptr(m.normal_B), H.ptr(m.normal_c) if with_c else None, H.ptr(m.weights),
                H.ptr(self.s), self.N, self.h, self.w, H.ptr(self.t))
 
-    wide_forms = not __import__('os').environ.get('FRTM_NO_WIDE')
-
     def _wgrad(self, feats, C, partial):
         """3x3 weight gradient of `feats` (N, C, h, w) against self.t as per-sample slabs; returns the number of slabs per sample."""
         if self.wide_parts:
@@ -169,9 +177,6 @@ class DiscriminatorLoss(MinimizationProblem):
         self._stencil(False)          # separate 4.6 us kernel: fusing it into the weight-gradient kernel measured slower (+8 us)
         parts = self._wgrad(self.mem.samples, self.c, self.partial)
         return self.partial, self.N * parts, self.c * 9, self.filter_regs[0] ** 2
-
-    # joint problem: a whole Gauss-Newton iteration as ONE resident launch (csrc/joint_persistent.hip) where the shape fits
-    persistent_joint = not __import__('os').environ.get('FRTM_NO_PERSISTENT_JOINT')
 
     def persistent_joint_args(self):
         """Operands of the resident form of the JOINT problem, or None (filter problem, maps wider than a wavefront, memory too large)."""
@@ -197,11 +202,6 @@ class DiscriminatorLoss(MinimizationProblem):
         m = self.mem
         return dict(X=m.samples, B=m.normal_B, c_map=m.normal_c, sw=m.weights, N=self.N, c=self.c, h=self.h, w=self.w,
                     w2=self.w2.data, lam2=self.filter_regs[0] ** 2)
-
-    # True: the projection part of the joint problem in its composed form (csrc/joint_fit.hip: k_joint_compose / k_joint_expand):
-    # the raw features are filtered with the composed 3x3 kernel p1 . w2 and their 3x3 weight gradient is expanded through w2 --
-    # two HBM-bound passes over the raw features per operator application instead of two Cin x c x pixels GEMMs.
-    composed = True
 
     def _use_composed(self):
         return bool(self.joint and self.composed and self.c <= 128 and self.Cin <= 2048 and 4 * (self.h + 2) * (self.w + 2) <= 64 * 1024)
@@ -275,8 +275,6 @@ class DiscriminatorLoss(MinimizationProblem):
         self._stencil(False)
         self._filter_grad(self.Z, self.filter_regs[1] ** 2, H.ptr(p2), 1.0, H.ptr(q[n1:]))
         self._project_grad(self.filter_regs[0] ** 2, H.ptr(p1), 1.0, H.ptr(q[:n1]))
-
-    fused = True        # joint problem: merged glue kernels (csrc/joint_fit.hip), 8 instead of 13 launches per CG iteration
 
     def has_pq(self):
         """Does apply_A_pq leave the partials of <p,q> itself (the solver then skips its own frtm_cg_pq launch)?"""
@@ -365,6 +363,15 @@ class DiscriminatorLoss(MinimizationProblem):
         return x / self.diag_M
 
 
+def leave_resident_forms():
+    """The resident solver forms are left for the rest of this process -- a fit was found incomplete, or a sequence is tracked again, because a
+    resident launch timed out, and a shared GPU does not become unshared: joint fits take the chain form, new target models start their filter
+    solver in the multi-kernel form.  A timed-out FILTER launch on its own (GaussNewtonCG.poll_persistent_abort) leaves the joint form on."""
+    DiscriminatorLoss.persistent_joint = False
+    GaussNewtonCG.persistent_joint = False
+    GaussNewtonCG.abort_seen_in_process = True
+
+
 _START_WEIGHTS = {}     # (Cin, c, device, generator state before the draw) -> (project.weight, filter.weight, generator state after it)
 
 
@@ -395,6 +402,27 @@ def _start_weights(cin, c, device):
 
 
 class Discriminator(nn.Module):
+
+    # True: on filter re-solve frames the "fewer than 10 pixels" early-out (reference :214) is taken ON THE DEVICE when the caller
+    # hands update() a device-resident pixel count and the re-solve runs as persistent launches: the tracking loop then has no
+    # device->host read at all and the host enqueues whole sequences ahead of the GPU.
+    device_early_out = True
+    # True: replay the first-frame fit as ONE hipGraph per instance.  Off by default -- measured on MI355X (round 2): the fit is bound
+    # by its chain of ~750 DEPENDENT small kernels (4.5-9 us each on the device, 134 us per CG iteration of kernel time), not by
+    # the host's launch rate: initialize() takes 23.4 ms for 2 objects either way, and ~800-node graphs per target model are a
+    # memory / driver burden for nothing.
+    graph_init = False
+    graph_init_after = int(os.environ.get('FRTM_GRAPH_INIT_AFTER', '0'))     # uses of an instance that run eagerly before init() is captured
+    resident_joint = True        # the tracker clears it for objects whose first-frame fits share the GPU on concurrent streams (chain form there)
+    persistent_first_fit = not os.environ.get('FRTM_NO_PERSISTENT_FIRST_FIT')
+    # True: the per-frame filter re-solves (update()) run as ONE persistent launch each when the memory's shape fits
+    # (csrc/cg_persistent.hip: w <= 64, c <= 96, N * ceil(h / 10) <= 240 -- the 480p configs; other sizes take the multi-kernel form).
+    # The fits inside init() never do: several objects are fitted on concurrent streams there, and two launches that each
+    # need all their workgroups resident at once must not share the GPU.
+    persistent_cg = True
+    # True: the memory inserts of a tracking window go out as ONE batched update (3 launches per window and object instead of 3 per
+    # frame and object) when everything is decided on the device anyway (guards_on_device(), no full-resolution label copies)
+    window_inserts = True
 
     def __init__(self, in_channels=1024, c_channels=96, out_channels=1,
                  init_iters=(5, 10, 10, 10, 10), update_iters=(10,), update_filters=True,
@@ -437,22 +465,12 @@ class Discriminator(nn.Module):
             p.requires_grad_(False)
         if not dev_ok:
             self.to(device)
-        self.frame_num = 0
-        self._solves_host = 0            # filter re-solves / "fewer than 10 pixels" early-outs decided on the host since init(); the ones
-        self._early_outs_host = 0        # decided on the device are counted there (num_solves / num_early_outs add the two)
-        self._guarded_runs = 0
-        self.num_persistent_aborts = 0   # persistent CG launches that timed out (GPU shared with another resident-hungry kernel)
-        self.update_optimizer = None
-        self.current_sample = None
-        self.memory = None
-        self._w1T = None
-        self._w1T_key = None
+        self._init_opt = None            # solver of the joint first-frame fit; refit_in_chain_form() restarts it from the start weights (kept
+        self._start_w = self._init_y = None      # only where a resident launch may run) and, with keep_hires, the full-resolution labels
+        self._init_calls = 0             # uses of this instance (graph_init_after); survives recycle()
+        self._new_object()
+        self._w1T = self._w1T_key = None
         self._ws = {}                    # recycled state: memories and problems of the previous object this instance served
-
-    # True: on filter re-solve frames the "fewer than 10 pixels" early-out (reference :214) is taken ON THE DEVICE when the caller
-    # hands update() a device-resident pixel count and the re-solve runs as persistent launches: the tracking loop then has no
-    # device->host read at all and the host enqueues whole sequences ahead of the GPU.
-    device_early_out = True
 
     def guards_on_device(self):
         """Will update() decide the early-out of a re-solve frame on the device (no host-side pixel count needed)?  True for every
@@ -494,16 +512,19 @@ class Discriminator(nn.Module):
         """Prepares this instance for a NEW object: fresh weights drawn like a newly constructed Discriminator, counters reset; the memories / problem buffers (~150 MB at 480p)
         stay allocated and are reused by the next init().  Nothing is freed or allocated on the device."""
         self._draw_start_weights()             # in place; a device-to-device copy when the generator state has been seen before
+        self._new_object()
+        self._invalidate()
+        return self
+
+    def _new_object(self):
         self.frame_num = 0
-        self._solves_host = 0
-        self._early_outs_host = 0
+        self._solves_host = 0            # filter re-solves / "fewer than 10 pixels" early-outs decided on the host since init(); the ones
+        self._early_outs_host = 0        # decided on the device are counted there (num_solves / num_early_outs add the two)
         self._guarded_runs = 0
-        self.num_persistent_aborts = 0
+        self.num_persistent_aborts = 0   # persistent CG launches that timed out (GPU shared with another resident-hungry kernel)
         self.update_optimizer = None
         self.current_sample = None
         self.memory = None
-        self._invalidate()
-        return self
 
     def _memory(self, tag, capacity, feature_size, labels_size, dev):
         m = self._ws.get(tag)
@@ -551,15 +572,6 @@ class Discriminator(nn.Module):
         H.require_gpu(y, 'compute_pixel_weights')
         return ops.pixel_weights(y, self._tf())
 
-    # True: replay the first-frame fit as ONE hipGraph per instance.  Off by default -- measured on MI355X (round 2): the fit is bound
-    # by its chain of ~750 DEPENDENT small kernels (4.5-9 us each on the device, 134 us per CG iteration of kernel time), not by
-    # the host's launch rate: initialize() takes 23.4 ms for 2 objects either way, and ~800-node graphs per target model are a
-    # memory / driver burden for nothing.
-    graph_init = False
-    graph_init_after = int(__import__('os').environ.get('FRTM_GRAPH_INIT_AFTER', '0'))     # uses of an instance that run eagerly before init() is captured
-    resident_joint = True        # the tracker clears it for objects whose first-frame fits share the GPU on concurrent streams (chain form there)
-    persistent_first_fit = not __import__('os').environ.get('FRTM_NO_PERSISTENT_FIRST_FIT')
-
     def init(self, x, y):
         """x: (K,Cin,h,w) features of the augmented first frame; y: (K,1,H,W) masks (reference :154-199).
 
@@ -576,46 +588,37 @@ class Discriminator(nn.Module):
         mem0 = self._memory('mem0', K, x.shape[-3:], y.shape[-3:], dev)
         mem0.initialize(x, y)
         self._init_y = y if self.keep_hires else None
-        if self.resident_init(K, x.shape[-2], x.shape[-1]) or (self.persistent_first_fit and self.persistent_cg):
-            # a resident launch may time out on a shared GPU: refit_in_chain_form() restarts the fit from these
-            self._start_w = (self.project.weight.detach().clone(), self.filter.weight.detach().clone())
-        else:
-            self._start_w = None
+        resident = self.resident_init(K, x.shape[-2], x.shape[-1]) or (self.persistent_first_fit and self.persistent_cg)
+        self._start_w = (self.project.weight.detach().clone(), self.filter.weight.detach().clone()) if resident else None      # (refit_in_chain_form() restarts from these)
         memory = self._memory('memory', self.memory_size, (c,) + tuple(x.shape[-2:]), y.shape[-3:], dev)
-        self._init_calls = getattr(self, '_init_calls', 0) + 1
+        self._init_calls += 1
         if not self.graph_init or self.keep_hires or torch.cuda.is_current_stream_capturing() or self._init_calls <= self.graph_init_after:
             opt = self._init_body(mem0, memory, None if not self.keep_hires else y)
-            opt.persistent = bool(self.persistent_cg) and not GaussNewtonCG.abort_seen_in_process
-            opt.reset_persistent_counts()
-            self.memory, self.update_optimizer = memory, opt
-            return
-        key = (K, tuple(x.shape), tuple(y.shape), str(dev), tuple(self.init_iters), tuple(self.update_iters),
-               tuple(self.filter_reg), tuple(self.precond), self.direction_forget_factor,
-               bool(self.persistent_first_fit and self.persistent_cg and not GaussNewtonCG.abort_seen_in_process),     # (the captured form of the first filter fit
-               bool(self.resident_joint and DiscriminatorLoss.persistent_joint and GaussNewtonCG.persistent_joint))    #  and of the joint fit: the
-        #                                 process-wide switches are part of it -- a graph captured with resident launches must not be replayed after they timed out)
-        ent = self._ws.get('init_graph')
-        if ent is None or ent['key'] != key or ent['mem0'] is not mem0 or ent['memory'] is not memory:
-            self._init_problems(mem0, memory)                    # buffers of problems / solvers exist before the capture
-            g = torch.cuda.CUDAGraph()
-            with H.capture(g):
-                opt = self._init_body(mem0, memory, None)
-            booked = bool(opt.persistent and opt._persistent_launched)
-            del opt._launched[:]                         # the capture booked the launches it RECORDED; the replays below book the ones that run
-            ent = self._ws['init_graph'] = dict(key=key, graph=g, mem0=mem0, memory=memory, opt=opt, w1T=self._w1T,
-                                                persistent_first_fit=booked)
-        ent['graph'].replay()
-        # host-side state as the eager path leaves it
-        memory.current_size = K
-        opt = ent['opt']
-        opt._has_p = True
-        if ent.get('persistent_first_fit'):            # the replayed resident launches of the filter fit, as _run_persistent books them
-            opt._persistent_launched = True
-            opt._launched.extend(int(v) for v in self.update_iters)
-            del opt._launched[:-64]
+        else:
+            # the captured forms of the first filter fit and of the joint fit are part of the key: a graph with resident launches is not replayed after a time-out
+            key = (K, tuple(x.shape), tuple(y.shape), str(dev), tuple(self.init_iters), tuple(self.update_iters),
+                   tuple(self.filter_reg), tuple(self.precond), self.direction_forget_factor,
+                   bool(self.persistent_first_fit and self.persistent_cg and not GaussNewtonCG.abort_seen_in_process),
+                   bool(self.resident_joint and DiscriminatorLoss.persistent_joint and GaussNewtonCG.persistent_joint))
+            ent = self._ws.get('init_graph')
+            if ent is None or ent['key'] != key or ent['mem0'] is not mem0 or ent['memory'] is not memory:
+                solvers = self._init_problems(mem0, memory)[2:]      # buffers of problems / solvers exist before the capture
+                for o in solvers:
+                    o.ledger.drop()          # an earlier object's bookings nobody settled: that object is gone (settling here would be a device->host read)
+                g = torch.cuda.CUDAGraph()
+                with H.capture(g):
+                    opt = self._init_body(mem0, memory, None)
+                # the capture booked the resident launches it RECORDED (joint fit, filter fit): every replay books them as the ones that run
+                booked = [(o, o.ledger.drop()) for o in solvers]
+                ent = self._ws['init_graph'] = dict(key=key, graph=g, mem0=mem0, memory=memory, opt=opt, w1T=self._w1T, booked=booked)
+            ent['graph'].replay()
+            memory.current_size = K                                  # host-side state as the eager path leaves it
+            for o, schedule in ent['booked']:
+                o.replayed(schedule)
+            self._w1T, self._w1T_key = ent['w1T'], (self.project.weight.data_ptr(), self.project.weight._version)
+            opt = ent['opt']
         opt.persistent = bool(self.persistent_cg) and not GaussNewtonCG.abort_seen_in_process
         opt.reset_persistent_counts()
-        self._w1T, self._w1T_key = ent['w1T'], (self.project.weight.data_ptr(), self.project.weight._version)
         self.memory, self.update_optimizer = memory, opt
 
     def _init_problems(self, mem0, memory):
@@ -636,12 +639,6 @@ class Discriminator(nn.Module):
         o.persistent = False
         o._alloc()
         return o
-
-    # True: the per-frame filter re-solves (update()) run as ONE persistent launch each when the memory's shape fits
-    # (csrc/cg_persistent.hip: w <= 64, c <= 96, N * ceil(h / 10) <= 240 -- the 480p configs; other sizes take the multi-kernel form).
-    # The fits inside init() never do: several objects are fitted on concurrent streams there, and two launches that each
-    # need all their workgroups resident at once must not share the GPU.
-    persistent_cg = True
 
     def _init_body(self, mem0, memory, y):
         """Reference :165-199 after the memory of raw samples has been filled.  Device work on this instance's buffers only."""
@@ -687,10 +684,6 @@ class Discriminator(nn.Module):
         """Number of coming frames up to and including the next filter re-solve (>= 1)."""
         return self.train_skipping - (self.frame_num % self.train_skipping)
 
-    # True: the memory inserts of a tracking window go out as ONE batched update (3 launches per window and object instead of 3 per
-    # frame and object) when everything is decided on the device anyway (guards_on_device(), no full-resolution label copies)
-    window_inserts = True
-
     def can_update_window(self, W):
         """May update_window() serve the next W frames?  Only the LAST of them may be a filter re-solve frame."""
         if not (self.window_inserts and self.update_filters and self.guards_on_device() and self.memory is not None and not self.memory.keep_hires):
@@ -717,24 +710,19 @@ class Discriminator(nn.Module):
         """Will init() on K samples of (in_channels, h, w) features run its joint fit in the resident form (csrc/joint_persistent.hip)?
         Such fits each want the whole chip: the tracker then enqueues the objects one after the other instead of on concurrent streams
         (two resident grids cannot be co-resident; measured with five objects on four streams: 51 ms instead of 40, and time-outs)."""
-        from .optimizer import GaussNewtonCG
         if not (DiscriminatorLoss.persistent_joint and GaussNewtonCG.persistent_joint and self.resident_joint):
             return False
         return H.lib().frtm_joint_persistent_plan(int(K), int(self.project.in_channels), int(self.project.out_channels), int(h), int(w), None) > 0
 
     def init_aborted(self):
-        """True if a resident launch of the first-frame fit timed out since the last call -- a Gauss-Newton iteration of the joint fit
-        (csrc/joint_persistent.hip) or the first filter fit on the fresh memory (csrc/cg_persistent.hip) is MISSING from this target model.
-        SYNCHRONISES (a few bytes).  The caller restarts the fit: refit_in_chain_form() while no frame has been tracked with the model
-        (Tracker.track on its first call after initialize()), otherwise the whole sequence (Tracker.run_sequence)."""
-        hit = False
-        o = getattr(self, '_init_opt', None)
+        """True if a resident launch of the first-frame fit timed out since the last call -- a Gauss-Newton iteration of the joint fit or the first
+        filter fit on the fresh memory is MISSING from this target model.  SYNCHRONISES (a few bytes).  The caller restarts the fit: refit_in_chain_form()
+        while no frame has been tracked with the model (Tracker.track on its first call after initialize()), else the sequence (Tracker.run_sequence)."""
+        o, u, hit = self._init_opt, self.update_optimizer, False
         if o is not None:
-            n = o.joint_aborts()
-            hit = n > getattr(o, '_joint_aborts_seen', 0)
-            o._joint_aborts_seen = n
-        u = self.update_optimizer
-        if u is not None and not hit and self.frame_num == 0 and u._persistent_launched:
+            seen, _ = o.ledger.seen[1], o.ledger.settle()
+            hit = o.ledger.seen[1] > seen                   # (the abort counter rose over the joint fit's launches)
+        if u is not None and not hit and self.frame_num == 0:
             hit = bool(u.poll_persistent_abort())
         return hit
 
@@ -742,18 +730,15 @@ class Discriminator(nn.Module):
         """Restarts the first-frame fit of init() from the weights it started from, every solver in the chain form (the resident forms are
         switched off for the process: a shared GPU does not become unshared).  Valid as long as nothing has been inserted into the memory
         since init(): the joint problem's memory of raw samples is still this instance's."""
-        if getattr(self, '_start_w', None) is None or self._ws.get('mem0') is None:
+        if self._start_w is None or self._ws.get('mem0') is None:
             raise RuntimeError('refit_in_chain_form: init() has not run (or not in a resident form)')
-        DiscriminatorLoss.persistent_joint = False
-        GaussNewtonCG.persistent_joint = False
-        GaussNewtonCG.abort_seen_in_process = True
+        leave_resident_forms()
         self.project.weight.data.copy_(self._start_w[0])
         self.filter.weight.data.copy_(self._start_w[1])
         self._invalidate()
         self._ws.pop('init_graph', None)
-        u = self.update_optimizer
-        if u is not None and u._persistent_launched:
-            u.poll_persistent_abort()               # (books the timed-out first filter fit: the fit below replaces it, update() must not "make it up")
+        if self.update_optimizer is not None:       # (settles a timed-out first filter fit: the fit below replaces it, update() must not "make it up")
+            self.update_optimizer.poll_persistent_abort()
         mem0, memory = self._ws['mem0'], self._ws['memory']
         memory.reset()
         opt = self._init_body(mem0, memory, self._init_y)

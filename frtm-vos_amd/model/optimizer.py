@@ -14,6 +14,8 @@ TensorList ops with Python in between.  Here
    (fp32, may overflow to inf => beta = 0), Polak-Ribiere beta clamped at 0, the skipped
    residual update on the last iteration, CG state carried across run() calls.
 """
+import os
+
 import torch
 
 from .. import _hip as H
@@ -47,9 +49,72 @@ class MinimizationProblem:
         return x
 
 
+def missed_iterations(launched, new_commits, new_aborts):
+    """``num_cg_iter`` of the booked resident launches (oldest first) that neither committed nor were skipped by the guard, given how far the device's
+    commit / abort counters rose over them.  Which ones is not recorded: the LAST are taken (the reference's update schedule has equal entries)."""
+    missed = min(new_aborts, max(len(launched) - new_commits, 0))
+    return launched[len(launched) - missed:] if missed > 0 else []
+
+
+class ResidentLedger:
+    """The host's books of one solver's resident launches over the device ``counters`` (GaussNewtonCG._gstats); ``mirror``: a pinned host word
+    that follows the abort counter.  It only keeps books: which switches a time-out flips is its callers' business."""
+
+    def __init__(self, counters, mirror):
+        self.counters, self.mirror = counters, mirror
+        self.launched = []           # num_cg_iter of the launches booked since the last settle (oldest first, the last 64)
+        self.pending = False         # something has been booked since the last settle
+        self.seen = (0, 0)           # (commits, aborts) at the last settle
+        self.used = False            # a launch has been booked since the solver was rewound: THIS object's fit took the resident form
+
+    def book(self, num_cg_iter, mirror=True):
+        """A launch that has just been enqueued; ``mirror``: enqueue the copy of the abort counter that peek() looks at behind it."""
+        self.pending = self.used = True
+        self.launched.append(int(num_cg_iter))
+        del self.launched[:-64]      # (bounded: callers that never settle -- benchmarks -- must not grow it)
+        if mirror:
+            self.mirror.copy_(self.counters[2:3], non_blocking=True)
+
+    def book_replayed(self, schedule):
+        """The resident launches of a run(schedule) that a replayed hipGraph has just enqueued (the graph holds no mirror copy)."""
+        for n in (n for n in schedule if n > 0):
+            self.book(n, mirror=False)
+
+    def drop(self):
+        """Forget (and hand back) what a hipGraph capture booked: it RECORDED those launches, the replays book the ones that run."""
+        dropped, self.launched = self.launched, []
+        return dropped
+
+    def peek(self):
+        """No wait: has the abort counter, as of the last mirror copy that landed, risen above the aborts already settled?"""
+        return self.pending and int(self.mirror[0]) > self.seen[1]
+
+    def settle(self):
+        """The one synchronising read (16 bytes; none while nothing is pending): the missed iterations since the last call."""
+        if not self.pending:
+            return []
+        launched, self.launched, self.pending = self.launched, [], False
+        _, _, aborts, commits = self.counters.tolist()
+        (commits0, aborts0), self.seen = self.seen, (commits, aborts)
+        return missed_iterations(launched, commits - commits0, aborts - aborts0)
+
+    def counts(self):
+        return tuple(int(v) for v in self.counters[:2].tolist())
+
+    def reset_counts(self):
+        H.fill(self.counters[:2], 0)
+
+
 class GaussNewtonCG:
 
     debug_abort = False              # tests (class or instance): the next persistent launches time out at their first barrier
+    # Set (for the whole process) once a persistent launch has timed out: the GPU is shared with something that keeps this solver's
+    # workgroups from becoming resident together, so new target models start in the multi-kernel form (Discriminator.init).
+    abort_seen_in_process = False
+    hierarchical_barrier = not os.environ.get('FRTM_FLAT_BARRIER')     # persistent launches: XCD-hierarchical grid barrier (False: one flat counter)
+    persistent = False          # filter problem: run a whole GN iteration as one persistent launch (csrc/cg_persistent.hip) when the shape fits
+    persistent_joint = True     # joint problem: resident form (csrc/joint_persistent.hip) where the problem offers it; switched off for the
+                                # whole process once a launch has timed out (discriminator.leave_resident_forms)
 
     def __init__(self, problem: MinimizationProblem, variable: TensorList, cg_eps=0.0, fletcher_reeves=True,
                  standard_alpha=True, direction_forget_factor=0, step_alpha=1.0):
@@ -65,8 +130,7 @@ class GaussNewtonCG:
         self.problem = problem
         self.x = variable
         self.cg_eps = cg_eps
-        self.step_alpha = step_alpha
-        self._step_alpha0 = step_alpha
+        self.step_alpha = self._step_alpha0 = step_alpha
         self.residuals = torch.zeros(0)
         self.external_losses = []
         self.internal_losses = []
@@ -78,14 +142,9 @@ class GaussNewtonCG:
         self._jbuf = None                # exchange buffers of the joint problem's resident form (_joint_exchange)
         self._guard = None               # (device count, minimum) while a guarded run() is in progress
         self._last_of_run = True         # the Gauss-Newton iteration being enqueued is the last of its run()
-        self._persistent_launched = False
-        self._joint_launched = False     # this object's fit has launched in the resident form of the joint problem
-        self._gstats = None              # device int32[4]: guarded runs completed / skipped by the device-side early-out, persistent launches
-                                         # aborted / persistent launches COMMITTED (wrote x and the solver state back)
-        self._launched = []              # num_cg_iter of every persistent launch since the last poll (oldest first)
-        self._committed_seen = 0
+        self._gstats = None              # device int32[4]: guarded runs completed / skipped on the device, resident launches ABORTED / COMMITTED
+        self.ledger = None               # ResidentLedger over _gstats (both exist from _stats() on): the host's books of the resident launches
         self._shadow = None              # snapshot of the solver state around a chain-form run with a device-side guard
-        self._aborts_handled = 0
 
     # ---- device state -------------------------------------------------------------------
     def _alloc(self):
@@ -161,9 +220,8 @@ class GaussNewtonCG:
         self._alloc()
         H.fill(self._all, 0.0)                              # _buf and _state are slices of this one allocation
         H.fill(self._state[:1], 1.0)
-        self._has_p = False
+        self._has_p = self.ledger.used = False
         self.step_alpha = self._step_alpha0
-        self._joint_launched = False     # (a pooled solver: joint_aborts() reads 0 until THIS object's fit has launched in the resident form)
         return self
 
     def reset_state(self):
@@ -173,10 +231,6 @@ class GaussNewtonCG:
             H.fill(self._state[:1], 1.0)
 
     # ---- solver ---------------------------------------------------------------------------
-    # Set (for the whole process) once a persistent launch has timed out: the GPU is shared with something that keeps this solver's
-    # workgroups from becoming resident together, so new target models start in the multi-kernel form (Discriminator.init).
-    abort_seen_in_process = False
-
     def can_guard(self):
         """True if run() can take a device-side early-out (``guard``): every problem with HIP operators can -- persistent launches
         test the guard themselves, the multi-kernel chain is rolled back on the device when the guard says so."""
@@ -184,10 +238,8 @@ class GaussNewtonCG:
 
     def _stats(self):
         if self._gstats is None:
-            dev = self.x[0].device
-            self._gstats = torch.zeros(4, dtype=torch.int32, device=dev)
-            # the abort counter (stats[2]) is mirrored into pinned host memory after every persistent launch: peek without waiting
-            self._abort_host = torch.zeros(1, dtype=torch.int32).pin_memory()
+            self._gstats = torch.zeros(4, dtype=torch.int32, device=self.x[0].device)
+            self.ledger = ResidentLedger(self._gstats, torch.zeros(1, dtype=torch.int32).pin_memory())
         return self._gstats
 
     def run(self, num_cg_iter, num_gn_iter=None, guard=None, guard_min=10):
@@ -249,17 +301,17 @@ class GaussNewtonCG:
             H.call('frtm_guarded_copy', H.ptr(v.data), self._shadow.data_ptr() + 4 * o, v.numel(), guard.data_ptr(), guard_min, 1, None, 0)
             o += v.numel()
 
-    hierarchical_barrier = not __import__('os').environ.get('FRTM_FLAT_BARRIER')     # persistent launches: XCD-hierarchical grid barrier (False: one flat counter)
-    persistent = False      # filter problem: run a whole GN iteration as one persistent launch (csrc/cg_persistent.hip) when the shape fits
-
     def _persistent_joint_plan(self):
         pr = self.problem
-        if not self.persistent_joint or not hasattr(pr, 'persistent_joint_args'):
-            return None
-        return pr.persistent_joint_args()
+        return pr.persistent_joint_args() if self.persistent_joint and hasattr(pr, 'persistent_joint_args') else None
 
-    persistent_joint = True     # joint problem: resident form (csrc/joint_persistent.hip) where the problem offers it; switched off for the
-                                # whole process once a launch has timed out (GaussNewtonCG.abort_seen_in_process)
+    def _launch_flags(self):
+        """Resets the CG state first if there is no forgetting factor, as every form of run_CG does; then the flags of its first direction
+        update: (has_p, apply_dff, fletcher_reeves, standard_alpha, the factor rho is divided by)."""
+        dff = float(self.direction_forget_factor)
+        if dff == 0:
+            self.reset_state()
+        return int(self._has_p), int(self._has_p and dff != 0), int(self.fletcher_reeves), int(self.standard_alpha), dff or 1.0
 
     def _run_persistent_joint(self, num_cg_iter, a):
         """linearize + run_CG + apply_step of run_GN_iter for the JOINT problem: two small launches (transpose, Z = w1 X) + ONE resident
@@ -267,115 +319,86 @@ class GaussNewtonCG:
         pr = self.problem
         pr.prepare_linearization()
         scratch, bar, hbar = self._joint_exchange(a['N'], a['Cin'], a['c'], a['h'], a['w'])
-        stats = self._stats()
-        dff = float(self.direction_forget_factor)
-        if dff == 0:
-            self.reset_state()
+        flags = self._launch_flags()
         n1, n2, m1, m2 = pr.vector_layout()
         H.call('frtm_joint_run_persistent', H.ptr(a['X']), H.ptr(a['Z']), H.ptr(a['B']), H.ptr(a['c_map']), H.ptr(a['sw']), a['N'], a['Cin'], a['c'],
                a['h'], a['w'], H.ptr(a['w1T']), H.ptr(a['w1']), H.ptr(a['w2']), H.ptr(self._buf), H.ptr(self._state), H.ptr(scratch), H.ptr(bar),
-               H.ptr(hbar) if self.hierarchical_barrier else None, int(num_cg_iter), int(self._has_p), int(self._has_p and dff != 0),
-               int(self.fletcher_reeves), int(self.standard_alpha), dff if dff != 0 else 1.0, float(a['lam1']), float(a['lam2']), 1.0 / m1, 1.0 / m2,
-               float(self.step_alpha), H.ptr(stats), int(bool(self.debug_abort)))
+               H.ptr(hbar) if self.hierarchical_barrier else None, int(num_cg_iter), *flags, float(a['lam1']), float(a['lam2']), 1.0 / m1, 1.0 / m2,
+               float(self.step_alpha), H.ptr(self._stats()), int(bool(self.debug_abort)))
         self._has_p = True
-        self._joint_launched = True
+        self.ledger.book(num_cg_iter, mirror=False)     # (nobody peeks at a first-frame fit: Discriminator.init_aborted settles it)
         if hasattr(pr, '_invalidate_views'):
             pr._invalidate_views()
 
     def joint_aborts(self):
-        """Aborted resident launches of the joint problem so far (stats[2]).  SYNCHRONISES; an aborted launch wrote nothing, i.e. that
-        Gauss-Newton iteration is MISSING from the fit: the caller re-runs the fit in the chain form (Discriminator.init / Tracker)."""
-        if not self._joint_launched or self._gstats is None:
-            return 0
-        return int(self._gstats[2].item())
+        """Aborted resident launches so far (stats[2]; 0 until THIS object's fit has launched in a resident form: solvers are pooled).  SYNCHRONISES;
+        an aborted launch wrote nothing: that Gauss-Newton iteration is MISSING from the fit, the caller re-runs it in the chain form."""
+        return int(self._gstats[2].item()) if self.ledger is not None and self.ledger.used else 0
 
     def _persistent_plan(self):
         pr = self.problem
-        args = pr.persistent_args() if hasattr(pr, 'persistent_args') else None
-        if args is None or not self.persistent:
-            return None
-        if H.lib().frtm_cg_persistent_plan(args['N'], args['c'], args['h'], args['w'], None, None) <= 0:
-            return None
-        return args
+        args = pr.persistent_args() if self.persistent and hasattr(pr, 'persistent_args') else None
+        fits = args is not None and H.lib().frtm_cg_persistent_plan(args['N'], args['c'], args['h'], args['w'], None, None) > 0
+        return args if fits else None
 
     def _run_persistent(self, num_cg_iter, a):
         """linearize + run_CG + apply_step of run_GN_iter in ONE launch; host-side bookkeeping as in run_CG."""
         slabs, qbuf, bar, hbar = self._filter_exchange()
-        stats = self._stats()
         guard, guard_min = self._guard if self._guard is not None else (None, 0)
-        dff = float(self.direction_forget_factor)
-        if dff == 0:
-            self.reset_state()
+        flags = self._launch_flags()
         n1, n2, m1, m2 = self.problem.vector_layout()
         H.call('frtm_cg_run_persistent_guarded', H.ptr(a['X']), H.ptr(a['B']), H.ptr(a['c_map']), H.ptr(a['sw']), a['N'], a['c'], a['h'], a['w'],
                H.ptr(a['w2']), H.ptr(self._buf), H.ptr(self._state), H.ptr(slabs), H.ptr(qbuf), H.ptr(bar),
-               int(num_cg_iter), int(self._has_p), int(self._has_p and dff != 0), int(self.fletcher_reeves), int(self.standard_alpha),
-               dff if dff != 0 else 1.0, float(a['lam2']), 1.0 / m1, float(self.step_alpha),
-               None if guard is None else guard.data_ptr(), guard_min, H.ptr(stats),
+               int(num_cg_iter), *flags, float(a['lam2']), 1.0 / m1, float(self.step_alpha),
+               None if guard is None else guard.data_ptr(), guard_min, H.ptr(self._stats()),
                int(guard is not None and self._last_of_run), int(bool(self.debug_abort)),
                H.ptr(hbar) if self.hierarchical_barrier else None)
         self._has_p = True
-        self._persistent_launched = True
-        self._launched.append(int(num_cg_iter))
-        del self._launched[:-64]          # (bounded: callers that never poll -- benchmarks -- must not grow it)
-        if not torch.cuda.is_current_stream_capturing():
-            self._abort_host.copy_(stats[2:3], non_blocking=True)
+        self.ledger.book(num_cg_iter, mirror=not torch.cuda.is_current_stream_capturing())
+
+    def replayed(self, schedule):
+        """The host-side state an eager run leaves behind, after a hipGraph of one was replayed; ``schedule``: what ResidentLedger.drop handed back."""
+        self._has_p = True
+        self.ledger.book_replayed(schedule)
 
     def reset_persistent_counts(self):
-        if self._gstats is not None:
-            H.fill(self._gstats[:2], 0)
+        if self.ledger is not None:
+            self.ledger.reset_counts()
 
     def persistent_counts(self):
         """(guarded runs completed, guarded runs that took the device-side early-out) so far.  SYNCHRONISES."""
-        if self._gstats is None:
-            return 0, 0
-        a, b = self._gstats[:2].tolist()
-        return int(a), int(b)
+        return (0, 0) if self.ledger is None else self.ledger.counts()
 
     def peek_persistent_abort(self):
-        """Non-blocking look at the abort counter as of the last persistent launch whose mirror copy has landed (may lag by a launch).
-        True -> call poll_persistent_abort() (which waits, switches to the multi-kernel form and tells the caller to re-run the solve)."""
-        return self._gstats is not None and self._persistent_launched and int(self._abort_host[0]) > self._aborts_handled
+        """No wait (ResidentLedger.peek; may lag by a launch).  True -> call poll_persistent_abort()."""
+        return self.ledger is not None and self.ledger.peek()
 
     def poll_persistent_abort(self):
-        """Non-empty list if persistent launches since the last poll gave up (their workgroups could not all become resident within the
-        spin time-out, e.g. another process holds the GPU's CUs): the ``num_cg_iter`` of the Gauss-Newton iterations that did NOT
-        happen.  An aborted launch leaves variable and solver state untouched -- commit and abort exclude each other on the device
-        (cg_persistent.hip: the write-back claims the abort word) -- so the CALLER re-runs exactly these iterations
-        (``run(missed)``; this solver is in the multi-kernel form from now on, and so is every solver created later in this process).
-        Launches skipped by the device-side guard neither commit nor abort and are not missed.  Empty list (falsy): nothing to do.
+        """The ``num_cg_iter`` of the Gauss-Newton iterations that did NOT happen because their persistent launch gave up since the last poll (its
+        workgroups could not all become resident within the spin time-out: the GPU is shared); empty: nothing to do.  An aborted launch leaves variable
+        and solver state untouched (commit xor abort, cg_persistent.hip), so the CALLER re-runs exactly these (``run(missed)``; this solver is in the
+        multi-kernel form from now on, and so is every solver created later in this process).  Launches skipped by the device-side guard are not missed.
         SYNCHRONISES (one 16-byte read); call it where the host waits anyway, or after peek_persistent_abort() said so."""
-        if not self._persistent_launched or self._gstats is None:
+        if self.ledger is None:
             return []
-        self._persistent_launched = False
-        launched, self._launched = self._launched, []
-        _, _, n, committed = self._gstats.tolist()
-        new_commits, self._committed_seen = committed - self._committed_seen, committed
-        if n <= self._aborts_handled:
-            return []
-        new_aborts, self._aborts_handled = n - self._aborts_handled, n
-        self.persistent = False
-        GaussNewtonCG.abort_seen_in_process = True
-        # the aborted launches are the ones that neither committed nor were skipped by the guard; which of the queue they were is not
-        # recorded -- with equal entries (the reference's update schedule is (10,)) it does not matter, otherwise the LAST ones are taken
-        missed = min(new_aborts, max(len(launched) - new_commits, 0)) if launched else new_aborts
-        return launched[len(launched) - missed:] if launched and missed else ([launched[-1]] * missed if launched else [])
+        aborts, missed = self.ledger.seen[1], self.ledger.settle()
+        if self.ledger.seen[1] > aborts:  # only the filter's form and the word for new target models (the joint form: leave_resident_forms)
+            self.persistent = False
+            GaussNewtonCG.abort_seen_in_process = True
+        return missed
 
     def run_GN_iter(self, num_cg_iter):
         aj = self._persistent_joint_plan() if num_cg_iter > 0 else None
+        a = self._persistent_plan() if num_cg_iter > 0 and aj is None else None
         if aj is not None:
             self._run_persistent_joint(num_cg_iter, aj)
-            self.step_alpha = min(self.step_alpha * 1.2, 1.0)
-            return
-        a = self._persistent_plan() if num_cg_iter > 0 else None
-        if a is not None:
+        elif a is not None:
             self._run_persistent(num_cg_iter, a)
-            self.step_alpha = min(self.step_alpha * 1.2, 1.0)
-            return
-        self.problem.linearize(self.x, self._buf[0])
-        if num_cg_iter > 0:
-            self.run_CG(num_cg_iter)
-            self.problem.apply_step(self.x, float(self.step_alpha), self._buf[5])
+        else:
+            self.problem.linearize(self.x, self._buf[0])
+            if num_cg_iter > 0:
+                self.run_CG(num_cg_iter)
+                self.problem.apply_step(self.x, float(self.step_alpha), self._buf[5])
         self.step_alpha = min(self.step_alpha * 1.2, 1.0)
 
     def run_CG(self, num_iter, x=None, eps=0.0):
@@ -386,25 +409,20 @@ class GaussNewtonCG:
         im1, im2 = 1.0 / m1, (1.0 / m2 if n2 else 1.0)
         b, r, r_prev, p, q, dx = [H.ptr(self._buf[i]) for i in range(6)]
         st, part = H.ptr(self._state), H.ptr(self._partial)
-        dff = float(self.direction_forget_factor)
-        if dff == 0:
-            self.reset_state()
-        apply_dff = int(self._has_p and dff != 0)
-        fr = int(self.fletcher_reeves)
-        H.call('frtm_cg_begin', b, r, r_prev, n1, n2, im1, im2, int(self._has_p and not fr), part)
+        has_p, apply_dff, fr, std_alpha, dff = self._launch_flags()
+        H.call('frtm_cg_begin', b, r, r_prev, n1, n2, im1, im2, int(has_p and not fr), part)
         fused = n2 == 0 and n1 <= 1024 and hasattr(pr, 'apply_A_partials')
         if fused:
             # small single-tensor problem: one fused vector kernel per iteration (3 launches per CG iteration in total)
-            H.call('frtm_cg_direction', r, p, n1, n2, im1, im2, int(self._has_p), apply_dff, fr, dff if dff != 0 else 1.0, st, part)
+            H.call('frtm_cg_direction', r, p, n1, n2, im1, im2, has_p, apply_dff, fr, dff, st, part)
             self._has_p = True
             for ii in range(num_iter):
                 slabs, nslab, stride, lam2 = pr.apply_A_partials(self._buf[3])
                 H.call('frtm_cg_step_small', H.ptr(slabs), nslab, stride, float(lam2), dx, r, r_prev, p, q, n1, im1, int(ii == 0),
-                       int(ii == num_iter - 1), int(self.standard_alpha), fr, st)
+                       int(ii == num_iter - 1), std_alpha, fr, st)
             return pr.views(self._buf[5]), []
         for ii in range(num_iter):
-            H.call('frtm_cg_direction', r, p, n1, n2, im1, im2, int(self._has_p), apply_dff if ii == 0 else 0, fr,
-                   dff if dff != 0 else 1.0, st, part)
+            H.call('frtm_cg_direction', r, p, n1, n2, im1, im2, has_p if ii == 0 else 1, apply_dff if ii == 0 else 0, fr, dff, st, part)
             self._has_p = True
             if getattr(pr, 'joint', False) and hasattr(pr, 'has_pq') and pr.has_pq():
                 # the problem's last kernel also leaves the partials of <p,q> (and <p,r>): no separate frtm_cg_pq launch
@@ -412,8 +430,7 @@ class GaussNewtonCG:
             else:
                 pr.apply_A(self._buf[3], self._buf[4])
                 H.call('frtm_cg_pq', p, q, None if self.standard_alpha else r, n1 + n2, part)
-            H.call('frtm_cg_update', dx, r, r_prev, p, q, n1, n2, im1, im2, int(ii == 0), int(ii == num_iter - 1),
-                   int(self.standard_alpha), st, part)
+            H.call('frtm_cg_update', dx, r, r_prev, p, q, n1, n2, im1, im2, int(ii == 0), int(ii == num_iter - 1), std_alpha, st, part)
         return pr.views(self._buf[5]), []
 
     # ---- generic form: any MinimizationProblem, operators through autograd (reference optimizer.py:77-157) -------------------
@@ -427,15 +444,11 @@ class GaussNewtonCG:
             jt_g = TensorList(torch.autograd.grad(list(f0), list(x), list(g), create_graph=True))     # J^T g, differentiable in g
         self._lin = (f0, g, jt_g)
         self._g['b'] = b = TensorList([-t.detach() for t in jt_g])
-        if num_cg_iter > 0:
-            delta = self._generic_CG(num_cg_iter, b)
-            for v in x:
-                v.detach_()
-            for v, d in zip(x, delta):
-                v.add_(d, alpha=float(self.step_alpha))
-        else:
-            for v in x:
-                v.detach_()
+        delta = self._generic_CG(num_cg_iter, b) if num_cg_iter > 0 else []
+        for v in x:
+            v.detach_()
+        for v, d in zip(x, delta):
+            v.add_(d, alpha=float(self.step_alpha))
         self.step_alpha = min(self.step_alpha * 1.2, 1.0)
         self._lin = None
 

@@ -31,7 +31,7 @@ import torch.nn.functional as F
 from .. import ops
 from .. import _hip as H
 from ..lib.utils import AverageMeter
-from .discriminator import Discriminator, apply_grouped
+from .discriminator import Discriminator, apply_grouped, leave_resident_forms
 
 
 _STREAMS = {}
@@ -551,11 +551,7 @@ class Tracker(nn.Module):
             torch.cuda.synchronize()
         missing = [d.init_aborted() for d in discs]
         if (any(missing) or any(late) or any(d.num_persistent_aborts > 0 for d in discs)) and not self._rerun:
-            from .discriminator import DiscriminatorLoss
-            from .optimizer import GaussNewtonCG
-            DiscriminatorLoss.persistent_joint = False
-            GaussNewtonCG.persistent_joint = False
-            GaussNewtonCG.abort_seen_in_process = True
+            leave_resident_forms()
             self._rerun = True
             try:
                 self.release_targets()

@@ -53,7 +53,7 @@ def test_config5_1080p_eight_objects_teacher_forced():
             if oid in solved:
                 a = prob.persistent_args()
                 assert H.lib().frtm_cg_persistent_plan(a['N'], a['c'], a['h'], a['w'], None, None) <= 0, oid
-                assert not opt._persistent_launched and not opt._launched, oid          # no resident launch: the chain ran
+                assert not opt.ledger.pending and not opt.ledger.launched, oid          # no resident launch: the chain ran
                 assert opt._shadow is not None, oid                                     # ... under the device-side guard (snapshot taken)
                 assert d.num_solves == 1 and d.num_early_outs == 0, (oid, d.num_solves, d.num_early_outs)
 

@@ -392,7 +392,7 @@ def test_fp64_arbiter_update_problem_1080p():
         d_h, d_o = [], []
         for k in range(2):
             opt.run((10,))
-            assert not opt._persistent_launched and not opt._launched          # the chain ran, no resident launch
+            assert not opt.ledger.pending and not opt.ledger.launched          # the chain ran, no resident launch
             e_h, e_o = rms(wv, f64[k]), rms(f32[k], f64[k])
             scale = float(f64[k].double().pow(2).mean().sqrt())
             print('update problem N=32 at 1080p, draw %d, run %d (multi-kernel, %d strips): rms |HIP - fp64| %.2e, |fp32 oracle - fp64| %.2e '
@@ -424,7 +424,7 @@ def test_fp64_arbiter_joint_first_frame_fit_1080p():
         for composed in (True, False):
             prob, opt, w1d, w2d = _hip_joint_fit(composed, X, Y, w1, w2, iters)
             assert prob.wide_parts > 0 and prob._use_composed() == composed, (prob.wide_parts, composed)
-            assert prob.persistent_joint_args() is None and not getattr(opt, '_joint_launched', False)      # no resident joint launch
+            assert prob.persistent_joint_args() is None and not opt.ledger.pending and not opt.ledger.launched      # no resident joint launch
             form = 'composed' if composed else 'GEMM'
             for name, hv, v32, v64 in (('project', w1d, a32, a64), ('filter', w2d, b32, b64)):
                 e_h, e_o = rms(hv, v64), rms(v32, v64)

@@ -165,7 +165,7 @@ def test_bench_starts_two_ranks_and_reports_the_update_work(tmp_path):
 def test_first_frame_fit_as_hipgraph_equals_eager_and_survives_recycling():
     """Discriminator.init replays its ~750 launches as one hipGraph per instance: same result as the launch-by-launch path
     (same kernels in the same order: bit-identical), also for the second and third object a recycled instance serves, and the
-    solver state it hands to update() continues like the eager one."""
+    solver state it hands to update() -- the host's books of its resident launches included -- continues like the eager one."""
     from frtm_vos_amd.model.discriminator import Discriminator
     torch.set_grad_enabled(False)
     g = torch.Generator().manual_seed(3)
@@ -188,6 +188,10 @@ def test_first_frame_fit_as_hipgraph_equals_eager_and_survives_recycling():
             d.project.weight.data.copy_(w1)
             d.filter.weight.data.copy_(w2)
             d.init(x, y)
+        # the replayed fit leaves the same books of resident launches behind as the eager one (GaussNewtonCG.replayed), none of them timed out
+        for og, oe in ((dg.update_optimizer, de.update_optimizer), (dg._init_opt, de._init_opt)):
+            assert og.ledger.pending == oe.ledger.pending and og.ledger.launched == oe.ledger.launched, (rnd, og.ledger.launched, oe.ledger.launched)
+        assert not dg.update_optimizer.poll_persistent_abort() and not de.update_optimizer.poll_persistent_abort()
         assert torch.equal(dg.project.weight, de.project.weight) and torch.equal(dg.filter.weight, de.filter.weight), rnd
         assert not torch.equal(dg.filter.weight, w2)
         assert torch.equal(dg.memory.samples, de.memory.samples) and torch.equal(dg.memory.normal_B, de.memory.normal_B)
@@ -333,7 +337,7 @@ def test_persistent_cg_run_equals_the_multi_kernel_form(shape):
             mem.update(ft, lab.to(DEV))
             opt.run((10,) if t != 1 else (5,))
             filt.append(wv.detach().clone())
-        assert not opt.poll_persistent_abort() and opt._persistent_launched == False
+        assert not opt.poll_persistent_abort() and opt.ledger.pending == False
         return torch.stack(filt)
 
     def rel(x, y):
@@ -395,7 +399,7 @@ def test_persistent_cg_matches_reference_fixture_g3(golden, spread_gate):
         opt.persistent = True
         assert opt._persistent_plan() is None            # problem.initialize() has not run yet: N unknown
         opt.run((10,))
-        assert opt._persistent_launched
+        assert opt.ledger.pending and opt.ledger.launched == [10]
 
         def rel(a, b):
             return float((a.cpu() - b).abs().max() / b.abs().max())

@@ -437,7 +437,7 @@ def test_first_filter_fit_takes_the_resident_form_and_an_abort_is_made_up():
         res.init(x0, y0)
         torch.cuda.synchronize()
         o = res.update_optimizer
-        assert o._persistent_launched and int(o._gstats[3]) == 1 and int(o._gstats[2]) == 0, 'the first fit did not take (or commit) the resident form'
+        assert o.ledger.pending and o.ledger.launched == [1] and int(o._gstats[3]) == 1 and int(o._gstats[2]) == 0, 'the first fit did not take (or commit) the resident form'
         fr, fp = ref.filter.weight.detach(), res.filter.weight.detach()
         assert float((fr - fp).abs().max()) <= 1e-4 * float(fr.abs().max())
         assert torch.equal(ref.project.weight, res.project.weight)
@@ -515,7 +515,7 @@ def test_three_objects_starting_together_are_fitted_in_the_chain_form_on_concurr
             assert d.resident_joint is want_resident, (n, d.resident_joint)
             assert bool(torch.isfinite(d.filter.weight).all()) and bool(torch.isfinite(d.project.weight).all())
             assert d.memory.current_size >= 5
-            assert getattr(d._init_opt, '_joint_launched', False) == want_resident or not want_resident
+            assert d._init_opt.ledger.used == want_resident or not want_resident
 
 
 @pytest.mark.parametrize('shape', [

@@ -44,7 +44,7 @@ def hashes():
                 for run, sched in enumerate(((10,), (5,))):
                     opt.run(sched)
                     print('filter', shape, 'hier' if hier else 'flat', 'FR' if fr else 'PR', 'run', run, sha(wv, opt._buf, opt._state, opt._stats()))
-                assert opt._persistent_launched and not opt.poll_persistent_abort()
+                assert opt.ledger.pending and not opt.poll_persistent_abort()
                 for count in (3, 50):                     # below / above guard_min = 10: the launch returns at once / runs
                     opt.run((3,), guard=torch.tensor([count], dtype=torch.int32, device=wv.device))
                     print('filter', shape, 'hier' if hier else 'flat', 'FR' if fr else 'PR', 'guard', count, sha(wv, opt._buf, opt._state, opt._stats()))
