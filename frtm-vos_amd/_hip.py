@@ -84,6 +84,7 @@ SIGNATURES = {
     'frtm_conv_bf16x3_launches': (ctypes.c_long, []),
     'frtm_conv_bf16x1_launches': (ctypes.c_long, []),
     'frtm_conv_bf16x1_3x3_launches': (ctypes.c_long, []),
+    'frtm_conv_bf16x1_3x3s2_launches': (ctypes.c_long, []),
     'frtm_telea_inpaint_u8': (I, [P, P, I, I, I, I, P]),
     'frtm_fastdiv_check': (ctypes.c_uint, [ctypes.c_uint, ctypes.c_uint]),
     'frtm_backbone_set_lanes': (I, [P, I]),
@@ -92,6 +93,7 @@ SIGNATURES = {
     'frtm_backbone_set_winograd4': (I, [P, I]),
     'frtm_backbone_set_precision': (I, [P, I]),
     'frtm_backbone_set_bf16_pieces': (I, [P, I]),
+    'frtm_backbone_set_bf16x1_3x3': (I, [P, I]),
     'frtm_merge_masks': (I, [P, I, I, P]),
     'frtm_merge_masks_frames': (I, [P, I, I, I, P]),
     'frtm_count_above': (I, [P, I, I, F, P, P]),

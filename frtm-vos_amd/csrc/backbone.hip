@@ -20,6 +20,7 @@ struct ConvL {
   float* wW6 = nullptr;         // ... and the 64 matrices of F(6x6,3x3) (FRTM_WLAYOUT_WINO6)
   float* wB = nullptr;          // convs a bf16x3 trunk routes (bf16x3_packs), bf16x3 trunks only: the three bf16 pieces (FRTM_WLAYOUT_BF16X3), packed lazily
   float* wB1 = nullptr;         // convs a bf16x1 trunk routes (bf16x1_packs), bf16x1 trunks only: one bf16 plane (FRTM_WLAYOUT_BF16X1), packed lazily
+  float* wB3 = nullptr;         // 3x3 convs a bf16x1_3x3 trunk routes (bf16x1_3x3_packs): the bf16 image of FRTM_WLAYOUT_BF16X1_3X3 (stride 1) / _S2 (stride 2), packed lazily
   bool loaded = false;
   int layout = 0;
   // per-conv launch plan (frtm_backbone_set_conv_plan; 0 = the planner's choice): the GEMM tile of the path the conv takes (direct 1x1 /
@@ -60,6 +61,7 @@ struct frtm_backbone {
   int precision = 0;           // frtm_backbone_set_precision / _set_bf16_pieces: 0 = fp32, 1 = bf16x3 for the routed stride-1 1x1 convs (bf16x3_route), 2 = bf16x1 (bf16x1_route)
   // FRTM_BF16X1_MIN_COLS=n (tests and measurements on small frames): a bf16x1 trunk routes EVERY eligible conv from n columns per launch on, instead of the measured table
   int bf16x1_min_cols = getenv("FRTM_BF16X1_MIN_COLS") ? atoi(getenv("FRTM_BF16X1_MIN_COLS")) : -1;
+  bool bf16x1_3x3 = false;     // frtm_backbone_set_bf16x1_3x3: with precision == 2, the routed 3x3 convs on bf16 MFMAs as well (bf16x1_3x3_route); stored whatever the precision is
   int generation = 0;          // bumped whenever an arena / workspace is (re)allocated: captured graphs of older generations are stale
 };
 
@@ -233,6 +235,67 @@ static int pack_bf16x1(ConvL& c, hipStream_t st) {
   return frtm_bf16x1_pack(c.wT, c.Cout, c.Cin, 1, (c.Cout + 31) / 32 * 32, c.wB1, st);
 }
 
+// The 3x3 pad-1 convs a bf16x1_3x3 trunk (frtm_backbone_set_bf16x1_3x3 on top of bf16x1) sends to the direct bf16 kernels -- stride 1 to
+// FRTM_WLAYOUT_BF16X1_3X3 (csrc/conv3x3_bf16x1.hip), stride 2 to FRTM_WLAYOUT_BF16X1_3X3_S2 (csrc/conv3x3s2_bf16x1.hip) -- by the rule of kBf16x1Rules:
+// a shape is routed from the column count at which its median beat the fp32 form the conv otherwise takes (Winograd F(6x6) / F(4x4) / F(2x2), or the
+// halo kernel for stride 2) by more than the fp32 arm's max - min, at 1 and at 8 frames of 480x854 (tools/bf16x1_trunk3x3_time.py ->
+// profiles/bf16x1_trunk3x3_time.txt).  A shape faster at 8 frames only is routed from its 8-frame column count on, one faster at 1 frame as well from its
+// 1-frame column count on.  Shapes that were not measured, or were not faster, stay fp32.  The images are packed when the flag first turns on:
+// bf16 [Cin/16][9][2][Mp][8], 18 Cin Cout bytes per conv -- every 3x3 conv of ResNet-101 (3 x 64^2 + 4 x 128^2 + 23 x 256^2 + 3 x 512^2 weights x 18 B)
+// comes to about 43 MB of device memory; only the convs the table (or FRTM_BF16X1_MIN_COLS) can route are packed.
+// us per launch, fp32 form / bf16 (automatic tile form), from that file:                    1 frame          8 frames
+struct Bf16x1Rule3x3 { int Cin, Cout, stride; long min_cols; };
+static const Bf16x1Rule3x3 kBf16x1Rules3x3[] = {
+  {64, 64, 1, 25680},     // layer1, 120x214, fused F(2x2)                                    15.2 / 11.3      77.2 / 30.2
+  {128, 128, 1, 6420},    // layer2, 60x107, F(6x6)                                           24.0 / 16.7      70.8 / 23.5
+  {256, 256, 1, 12960},   // layer3, 30x54, F(6x6): slower at 1 frame                         22.0 / 28.4      57.3 / 30.4
+  {512, 512, 1, 3240},    // layer4, 15x27, F(4x4): slower at 1 frame                         31.1 / 50.6      62.4 / 51.6
+  {128, 128, 2, 6420},    // ResNet-50 / 101 layer2 opener, -> 60x107, halo                   40.2 / 31.5     193.8 / 52.1
+  {256, 256, 2, 12960},   // ... layer3 opener, -> 30x54: slower at 1 frame                   45.3 / 56.7     203.0 / 58.0
+  {512, 512, 2, 3240},    // ... layer4 opener, -> 15x27: slower at 1 frame                   49.7 / 101.7    201.0 / 102.1
+  {64, 128, 2, 6420},     // ResNet-18 / 34 layer2 opener, -> 60x107, halo                    30.5 / 18.3     105.2 / 29.8
+  {128, 256, 2, 1620},    // ... layer3 opener, -> 30x54                                      31.8 / 30.8     107.1 / 32.3
+  {256, 512, 2, 3240},    // ... layer4 opener, -> 15x27: slower at 1 frame                   34.4 / 53.2     103.6 / 53.9
+};
+static const Bf16x1Rule3x3* bf16x1_3x3_rule(const ConvL& c) {
+  for (const Bf16x1Rule3x3& r : kBf16x1Rules3x3)
+    if (r.Cin == c.Cin && r.Cout == c.Cout && r.stride == c.stride) return &r;
+  return nullptr;
+}
+static bool bf16x1_3x3_eligible(const ConvL& c) { return c.ks == 3 && c.pad == 1 && (c.stride == 1 || c.stride == 2); }
+static bool bf16x1_3x3_packs(const frtm_backbone* bb, const ConvL& c) { return bf16x1_3x3_eligible(c) && (bb->bf16x1_min_cols >= 0 || bf16x1_3x3_rule(c)); }
+static bool bf16x1_3x3_route(const frtm_backbone* bb, const ConvL& c, int B, int Ho, int Wo) {
+  if (!bf16x1_3x3_packs(bb, c)) return false;
+  const long cols = (long)B * Ho * Wo;
+  return cols >= (bb->bf16x1_min_cols >= 0 ? (long)bb->bf16x1_min_cols : bf16x1_3x3_rule(c)->min_cols);
+}
+
+// the halo image of a 3x3 conv (k_pack_weights_halo: wT[((ci / 8 * 9 + tap) * 8 + ci % 8) * Mp32 + m], exact fp32) back to OIHW
+__global__ __launch_bounds__(256) void k_halo_to_oihw(const float* __restrict__ wT, int Cout, int Cin, int Mp, float* __restrict__ w) {
+  const size_t total = (size_t)Cout * Cin * 9;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    const int tap = (int)(i % 9), ci = (int)((i / 9) % Cin), m = (int)(i / ((size_t)9 * Cin));
+    w[i] = wT[((size_t)(ci / 8 * 9 + tap) * 8 + ci % 8) * Mp + m];
+  }
+}
+
+// the bf16 3x3 image of an eligible conv, from its OIHW weights (frtm_backbone_set_conv) or, w_oihw == nullptr, from its halo image
+static int pack_bf16x1_3x3(ConvL& c, const float* w_oihw, hipStream_t st) {
+  if (!c.wB3) FRTM_HIP(hipMalloc((void**)&c.wB3, FRTM_CONV_BF16X1_3X3_ELEMS(c.Cout, c.Cin) * sizeof(float)));
+  const int layout = c.stride == 2 ? FRTM_WLAYOUT_BF16X1_3X3_S2 : FRTM_WLAYOUT_BF16X1_3X3;
+  if (w_oihw) return frtm_conv_pack_weights(w_oihw, c.Cout, c.Cin, 3, layout, c.wB3, nullptr, (frtm_stream_t)st);
+  float* tmp = nullptr;
+  const size_t total = (size_t)c.Cout * c.Cin * 9;
+  FRTM_HIP(hipMalloc((void**)&tmp, total * sizeof(float)));
+  k_halo_to_oihw<<<(int)std::min<size_t>((total + 255) / 256, 2048), 256, 0, st>>>(c.wT, c.Cout, c.Cin, (c.Cout + 31) / 32 * 32, tmp);
+  int rc = FRTM_ERR_HIP;
+  if (hipGetLastError() == hipSuccess) rc = frtm_conv_pack_weights(tmp, c.Cout, c.Cin, 3, layout, c.wB3, nullptr, (frtm_stream_t)st);
+  else frtm_set_error("backbone: k_halo_to_oihw failed to launch");
+  (void)hipStreamSynchronize(st);           // the temporary dies here
+  (void)hipFree(tmp);
+  return rc;
+}
+
 static int run_conv(frtm_backbone* bb, Lane& ln, int idx, int B, int Hin, int Win, const float* in, const float* residual, int relu,
                     float* out, int* Ho, int* Wo, hipStream_t st, int pad_override = -1) {
   ConvL& c = bb->convs[idx];
@@ -254,6 +317,14 @@ static int run_conv(frtm_backbone* bb, Lane& ln, int idx, int B, int Hin, int Wi
   d.ws_elems = (int)std::min<size_t>(ln.ws_elems, 0x7fffffff);
   bb->last_launches += 1;
   bb->last_flops += 2.0 * c.Cout * (double)B * (*Ho) * (*Wo) * c.Cin * c.ks * c.ks;      // algorithmic (direct-form) FLOPs
+  // bf16x1_3x3 trunks: the routed 3x3 convs on bf16 MFMAs (direct form: full MACs), before any Winograd form is considered
+  if (bb->precision == 2 && bb->bf16x1_3x3 && c.wB3 && pad == 1 && !c.plan_tile && !c.plan_splitk && bf16x1_3x3_route(bb, c, B, *Ho, *Wo)) {
+    d.w_layout = c.stride == 2 ? FRTM_WLAYOUT_BF16X1_3X3_S2 : FRTM_WLAYOUT_BF16X1_3X3;
+    d.splitk = 1;
+    bb->last_flops_exec += 2.0 * c.Cout * (double)B * (*Ho) * (*Wo) * c.Cin * 9.0;
+    bb->last_flops_form[0] += 2.0 * c.Cout * (double)B * (*Ho) * (*Wo) * c.Cin * 9.0;
+    return frtm_conv2d(&d, in, c.wB3, nullptr, c.scale, c.shift, residual, out, nullptr, st);
+  }
   // Winograd F(4x4,3x3) / F(6x6,3x3), three-launch form (conv_wino4.hip), for the wide 3x3 stride-1 convs: 2.25 / 1.78 multiplications
   // per output instead of 4; eligible when the products fill the chip as one GEMM launch and the output tiles waste < 25 % on the
   // map's edges; of the two, the form with fewer products = (m+2)^2 x padded tile count (30x54: 6x6 tiles fit exactly, 64 x 384 against
@@ -469,6 +540,7 @@ int frtm_backbone_destroy(frtm_backbone_t* bb) {
     if (c.wW6) (void)hipFree(c.wW6);
     if (c.wB) (void)hipFree(c.wB);
     if (c.wB1) (void)hipFree(c.wB1);
+    if (c.wB3) (void)hipFree(c.wB3);
     if (c.scale) (void)hipFree(c.scale);
     if (c.shift) (void)hipFree(c.shift);
     if (c.ktab) (void)hipFree(c.ktab);
@@ -524,6 +596,10 @@ int frtm_backbone_set_conv(frtm_backbone_t* bb, int idx, const float* w_oihw, co
   }
   if (bf16x1_packs(bb, c) && (c.wB1 || bb->precision == 2)) {
     rc = pack_bf16x1(c, st);
+    if (rc) return rc;
+  }
+  if (bf16x1_3x3_packs(bb, c) && (c.wB3 || bb->bf16x1_3x3)) {
+    rc = pack_bf16x1_3x3(c, w_oihw, st);
     if (rc) return rc;
   }
   if (c.ks == 3 && c.stride == 1 && c.pad == 1) {
@@ -585,6 +661,28 @@ int frtm_backbone_set_bf16_pieces(frtm_backbone_t* bb, int pieces) {
   FRTM_CHECK_ARG(bb, "frtm_backbone_set_bf16_pieces: null handle");
   FRTM_CHECK_ARG(pieces == 0 || pieces == 1 || pieces == 3, "frtm_backbone_set_bf16_pieces: pieces must be 0 (fp32), 1 (bf16x1) or 3 (bf16x3), got %d", pieces);
   return set_precision_mode(bb, pieces == 3 ? 1 : pieces == 1 ? 2 : 0);
+}
+
+int frtm_backbone_set_bf16x1_3x3(frtm_backbone_t* bb, int on) {
+  FRTM_CHECK_ARG(bb, "frtm_backbone_set_bf16x1_3x3: null handle");
+  FRTM_CHECK_ARG(on == 0 || on == 1, "frtm_backbone_set_bf16x1_3x3: on must be 0 or 1, got %d", on);
+  if (on) {
+    auto wants = [&](const ConvL& c) { return c.loaded && bf16x1_3x3_packs(bb, c) && !c.wB3; };
+    bool pack = false;
+    for (auto& c : bb->convs) pack |= wants(c);
+    if (pack) {          // a configuration call, as set_precision_mode: the halo images may come from any stream, the bf16 ones are ready on return
+      FRTM_HIP(hipDeviceSynchronize());
+      for (auto& c : bb->convs)
+        if (wants(c)) {
+          int rc = pack_bf16x1_3x3(c, nullptr, nullptr);
+          if (rc) return rc;
+        }
+      FRTM_HIP(hipDeviceSynchronize());
+    }
+  }
+  if ((on != 0) != bb->bf16x1_3x3) bb->generation += 1;       // captured graphs hold the other kernels
+  bb->bf16x1_3x3 = on != 0;
+  return FRTM_OK;
 }
 
 int frtm_backbone_set_winograd4(frtm_backbone_t* bb, int enable) {

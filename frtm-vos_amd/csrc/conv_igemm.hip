@@ -41,6 +41,7 @@ int frtm_bf16x1_launch(ConvParams p, int tile, hipStream_t st);
 // conv3x3_bf16x1.hip
 int frtm_bf16x1_3x3_pack(const float* src, int Cout, int Cin, float* out, hipStream_t st);
 int frtm_bf16x1_3x3_launch(ConvParams p, int tile, hipStream_t st);
+int frtm_bf16x1_3x3s2_launch(ConvParams p, int tile, hipStream_t st);
 
 static thread_local char t_conv_trace[256];        // space-separated kernel names (conv_common.h: conv_trace)
 static thread_local int t_conv_trace_len = 0;
@@ -1021,6 +1022,10 @@ int frtm_conv_pack_weights(const float* w_oihw, int Cout, int Cin, int ksize, in
     FRTM_CHECK_ARG(ksize == 3, "frtm_conv_pack_weights: the bf16x1 3x3 layout is for 3x3 kernels (got ksize %d)", ksize);
     return frtm_bf16x1_3x3_pack(w_oihw, Cout, Cin, wT, (hipStream_t)stream);
   }
+  if (layout == FRTM_WLAYOUT_BF16X1_3X3_S2) {           // the image of layout 7, byte for byte
+    FRTM_CHECK_ARG(ksize == 3, "frtm_conv_pack_weights: the bf16x1 3x3 stride-2 layout is for 3x3 kernels (got ksize %d)", ksize);
+    return frtm_bf16x1_3x3_pack(w_oihw, Cout, Cin, wT, (hipStream_t)stream);
+  }
   if (layout == FRTM_WLAYOUT_HALO3X3) {
     FRTM_CHECK_ARG(ksize == 3, "frtm_conv_pack_weights: the halo layout is for 3x3 kernels");
     const size_t total = (size_t)ceil_div(Cin, HCI) * HK * ((Cout + 31) / 32 * 32);
@@ -1096,6 +1101,15 @@ int frtm_conv2d(const frtm_conv_desc* d, const float* in, const float* wT, const
     FRTM_CHECK_ARG(d->w_pitch == 0, "frtm_conv2d: the bf16x1 3x3 layout takes its packed image only (w_pitch %d)", d->w_pitch);
     FRTM_CHECK_ARG(d->splitk >= 0 && d->splitk <= 1, "frtm_conv2d: the bf16x1 3x3 layout has no split-K (splitk %d)", d->splitk);
     return frtm_bf16x1_3x3_launch(p, d->tile, (hipStream_t)stream);
+  }
+  if (d->w_layout == FRTM_WLAYOUT_BF16X1_3X3_S2) {
+    FRTM_CHECK_ARG(d->ksize == 3, "frtm_conv2d: the bf16x1 3x3 stride-2 layout needs ksize 3 (got %d)", d->ksize);
+    FRTM_CHECK_ARG(d->stride == 2, "frtm_conv2d: the bf16x1 3x3 stride-2 layout needs stride 2 (got %d)", d->stride);
+    FRTM_CHECK_ARG(d->pad == 1, "frtm_conv2d: the bf16x1 3x3 stride-2 layout needs pad 1 (got %d)", d->pad);
+    FRTM_CHECK_ARG(!d->out_transposed, "frtm_conv2d: the bf16x1 3x3 stride-2 layout writes NCHW only (out_transposed is set)");
+    FRTM_CHECK_ARG(d->w_pitch == 0, "frtm_conv2d: the bf16x1 3x3 stride-2 layout takes its packed image only (w_pitch %d)", d->w_pitch);
+    FRTM_CHECK_ARG(d->splitk >= 0 && d->splitk <= 1, "frtm_conv2d: the bf16x1 3x3 stride-2 layout has no split-K (splitk %d)", d->splitk);
+    return frtm_bf16x1_3x3s2_launch(p, d->tile, (hipStream_t)stream);
   }
   const bool is1x1 = (d->ksize == 1 && d->pad == 0);
   FRTM_CHECK_ARG(is1x1 || ktab || d->w_layout == FRTM_WLAYOUT_HALO3X3, "frtm_conv2d: ktab required for ksize > 1");

@@ -24,9 +24,9 @@ class Parameters:
                  ytvos_fork_solver=False, refiner_graphs=None, aug_fill='telea', upsampler='compat', trunk_precision='fp32',
                  refiner_precision='fp32'):
         self.device = device
-        if trunk_precision not in ('fp32', 'bf16x3', 'bf16x1'):
-            raise ValueError("trunk_precision must be 'fp32', 'bf16x3' or 'bf16x1', got %r" % (trunk_precision,))
-        self.trunk_precision = trunk_precision    # 'fp32', 'bf16x3' or 'bf16x1': the trunk's routed stride-1 1x1 convs on bf16 pieces (ResnetFeatureExtractor.precision)
+        if trunk_precision not in ('fp32', 'bf16x3', 'bf16x1', 'bf16x1_3x3'):
+            raise ValueError("trunk_precision must be 'fp32', 'bf16x3', 'bf16x1' or 'bf16x1_3x3', got %r" % (trunk_precision,))
+        self.trunk_precision = trunk_precision    # 'fp32', 'bf16x3', 'bf16x1': the trunk's routed stride-1 1x1 convs on bf16 pieces; 'bf16x1_3x3': its routed 3x3 convs too (ResnetFeatureExtractor.precision)
         if refiner_precision not in ('fp32', 'bf16x1'):
             raise ValueError("refiner_precision must be 'fp32' or 'bf16x1', got %r" % (refiner_precision,))
         self.refiner_precision = refiner_precision    # 'fp32' or 'bf16x1': the refiner's routed 3x3 convs on one bf16 piece per operand (SegNetwork.precision)
@@ -136,10 +136,11 @@ def parse_args(argv=None):
                     help="refiner head: 'compat' (BackwardCompatibleUpsampler, the reference's default) or 'bicubic' (Upsampler, the fork's head)")
     ap.add_argument('--ytvos-fork', action='store_true',
                     help="a checkpoint of the reference's YouTube-VOS fork: shorthand for --ytvos-solver --ytvos-merge --upsampler bicubic")
-    ap.add_argument('--trunk-precision', choices=['fp32', 'bf16x3', 'bf16x1'], default='fp32',
+    ap.add_argument('--trunk-precision', choices=['fp32', 'bf16x3', 'bf16x1', 'bf16x1_3x3'], default='fp32',
                     help="'bf16x3': the routed stride-1 1x1 trunk convs on three bf16 pieces per operand (not bitwise fp32: 0.78-1.40x the fp32 kernels' max error against fp64; "
                          "no measurable speed-up of the trunk or the tracker); 'bf16x1': on one bf16 piece per operand, fp32 accumulation (NOT fp32-level arithmetic: "
-                         "up to 2^-7 relative error per product); README, DESIGN.md section 4")
+                         "up to 2^-7 relative error per product); 'bf16x1_3x3': bf16x1 with the routed 3x3 convs of stride 1 and 2 on one bf16 piece as well (the "
+                         "only bf16 mode that reaches ResNet-18); README, DESIGN.md section 4")
     ap.add_argument('--refiner-precision', choices=['fp32', 'bf16x1'], default='fp32',
                     help="'bf16x1': the refiner's routed 3x3 convs on one bf16 piece per operand, fp32 accumulation (NOT fp32-level arithmetic: up to 2^-7 "
                          "relative error per product; the 1x1 convs and the glue stay fp32); README, DESIGN.md section 4")

@@ -115,7 +115,8 @@ class ResNetParams(nn.Module):
         return self
 
 
-_PRECISIONS = {'fp32': 0, 'bf16x3': 3, 'bf16x1': 1}     # bf16 pieces per operand (frtm_backbone_set_bf16_pieces)
+# bf16 pieces per operand (frtm_backbone_set_bf16_pieces); 'bf16x1_3x3' is bf16x1 with the routed 3x3 convs on bf16 MFMAs as well (frtm_backbone_set_bf16x1_3x3)
+_PRECISIONS = {'fp32': 0, 'bf16x3': 3, 'bf16x1': 1, 'bf16x1_3x3': 1}
 
 
 class ResnetFeatureExtractor:
@@ -199,8 +200,14 @@ class ResnetFeatureExtractor:
     def precision(self):
         """'fp32' (default), 'bf16x3' or 'bf16x1': the routed stride-1 1x1 convs of the trunk on three bf16 pieces per operand (fp32-level error), or
         on one (operands rounded to bf16, fp32 accumulation: NOT fp32-level arithmetic) (frtm_backbone_set_bf16_pieces; the error bounds and the
-        routed shapes: DESIGN.md sections 4 and 9).  Every other conv stays fp32."""
+        routed shapes: DESIGN.md sections 4 and 9).  Every other conv stays fp32.  'bf16x1_3x3': bf16x1, and the routed 3x3 pad-1 convs of stride 1
+        and 2 on one bf16 piece per operand as well (frtm_backbone_set_bf16x1_3x3) -- the only reduced-precision mode that reaches the BasicBlock
+        trunks (ResNet-18 / 34 have no stride-1 1x1 conv)."""
         return self._precision
+
+    def _apply_precision(self, mode):
+        H.call_nostream('frtm_backbone_set_bf16_pieces', self._handle, _PRECISIONS[mode])
+        H.call_nostream('frtm_backbone_set_bf16x1_3x3', self._handle, int(mode == 'bf16x1_3x3'))
 
     @precision.setter
     def precision(self, mode):
@@ -208,7 +215,7 @@ class ResnetFeatureExtractor:
             raise ValueError('precision must be one of %s, got %r' % (sorted(_PRECISIONS), mode))
         if self._handle is not None:
             with torch.cuda.device(self.device):
-                H.call_nostream('frtm_backbone_set_bf16_pieces', self._handle, _PRECISIONS[mode])      # raises: the mode stays as it was
+                self._apply_precision(mode)      # raises: the mode stays as it was
             self._out_cache.clear()           # captured graphs hold the other kernels
         self._precision = mode
 
@@ -281,7 +288,7 @@ class ResnetFeatureExtractor:
                 H.call('frtm_backbone_set_conv', self._handle, i, H.ptr(cv.weight.data.float().contiguous()),
                        H.ptr(scale), H.ptr(shift))
             torch.cuda.current_stream().synchronize()      # the temporaries above die with this scope
-            H.call_nostream('frtm_backbone_set_bf16_pieces', self._handle, _PRECISIONS[self._precision])
+            self._apply_precision(self._precision)
 
     def lane_streams(self):
         """The native trunk's internal streams (lanes 1.. of set 0) as torch streams: a caller that runs other work NEXT TO a pass places

@@ -52,21 +52,23 @@ def bf16x1_3x3_elems(Cout, Cin):
     return 9 * ((Cin + 15) // 16 * 16) * ((Cout + 31) // 32 * 32) // 2
 
 
-def pack_weights(w_oihw, halo=None, wino=False, wino4=False, wino6=False, bf16x3=False, bf16x1=False):
+def pack_weights(w_oihw, halo=None, wino=False, wino4=False, wino6=False, bf16x3=False, bf16x1=False, stride=1):
     """(Cout,Cin,k,k) -> packed GEMM weights (+ ktab for k > 1).  3x3 kernels default to the halo layout
     (valid for pad-1 convs of stride 1 or 2); wino=True: Winograd F(2x2,3x3) image (stride 1, pad 1); wino4=True: the 36 transformed
     weight matrices of Winograd F(4x4,3x3) (FRTM_WLAYOUT_WINO4; conv2d then needs ``ws`` = wino4_workspace(...)); wino6=True: the 64 of
     F(6x6,3x3) (FRTM_WLAYOUT_WINO6, ``ws`` = wino4_workspace(..., m=6)); bf16x3=True: the three bf16 pieces of a 1x1 kernel (FRTM_WLAYOUT_BF16X3,
     Cin % 16 == 0; conv2d with ``w_layout=5``); bf16x1=True: the weights rounded to one bf16 plane (FRTM_WLAYOUT_BF16X1, Cin % 16 == 0; conv2d with
     ``w_layout=6``, ``tile`` 0 = automatic, 1 = 128x64, 2 = 64x64) -- or, for a 3x3 kernel, the bf16 image of the direct 3x3 form
-    (FRTM_WLAYOUT_BF16X1_3X3, any Cin; conv2d with ``w_layout=7``, stride 1, pad 1, ``tile`` 0 = automatic, 1 = 64, 2 = 96 output channels).
+    (FRTM_WLAYOUT_BF16X1_3X3, any Cin; conv2d with ``w_layout=7``, stride 1, pad 1, ``tile`` 0 = automatic, 1 = 64, 2 = 96 output channels); with
+    ``stride=2`` the same image under FRTM_WLAYOUT_BF16X1_3X3_S2 (conv2d with ``w_layout=8``, stride 2, pad 1).
     Returns (wT, ktab, layout)."""
     w = w_oihw.detach().float().contiguous()
     Cout, Cin, k, _ = w.shape
     if bf16x1 and k == 3:
+        layout = 8 if stride == 2 else 7
         wT = torch.zeros(bf16x1_3x3_elems(Cout, Cin), device=w.device)
-        H.call('frtm_conv_pack_weights', H.ptr(w), Cout, Cin, k, 7, H.ptr(wT), None)
-        return wT, None, 7
+        H.call('frtm_conv_pack_weights', H.ptr(w), Cout, Cin, k, layout, H.ptr(wT), None)
+        return wT, None, layout
     if bf16x1:
         wT = torch.zeros(bf16x1_elems(Cout, Cin), device=w.device)
         H.call('frtm_conv_pack_weights', H.ptr(w), Cout, Cin, k, 6, H.ptr(wT), None)

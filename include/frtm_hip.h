@@ -325,6 +325,11 @@ typedef struct {
 #define FRTM_CONV_BF16X1_3X3_ELEMS(Cout, Cin) ((size_t)9 * (((Cin) + 15) / 16 * 16) * (((Cout) + 31) / 32 * 32) / 2)
 #define FRTM_BF16X1_3X3_TILE_64 1
 #define FRTM_BF16X1_3X3_TILE_96 2
+/* The same for the 3x3 STRIDE-2 convs (opt-in bf16x1_3x3 trunk mode, csrc/conv3x3s2_bf16x1.hip): 3x3, stride 2, pad 1 (zeros), NCHW output, w_pitch 0,
+   splitk 0 or 1; any Cin, Cout, B, H, W; Ho = (Hin - 1) / 2 + 1, Wo likewise.  Arithmetic, semantics, error bound, `tile` values and the weight image are
+   those of FRTM_WLAYOUT_BF16X1_3X3: frtm_conv_pack_weights writes the SAME FRTM_CONV_BF16X1_3X3_ELEMS floats under either layout number.  Other
+   descriptors (stride 1 among them) return FRTM_ERR_ARG; FRTM_WLAYOUT_BF16X1_3X3 (7) keeps refusing stride 2. */
+#define FRTM_WLAYOUT_BF16X1_3X3_S2 8
 #define FRTM_WINO_MIN_BLOCKS 512   /* 8x8 output blocks x 32-channel tiles below which callers prefer HALO3X3 + split-K */
 #define FRTM_CONV_PACKED_ELEMS(Cout, Cin, k) \
   (((((Cin) * (k) * (k) + 31) / 32 * 32) > (((Cin) + 7) / 8 * 72) ? (((Cin) * (k) * (k) + 31) / 32 * 32) : (((Cin) + 7) / 8 * 72)) * (((Cout) + 31) / 32 * 32))
@@ -405,6 +410,8 @@ long frtm_conv_bf16x3_launches(void);
 long frtm_conv_bf16x1_launches(void);
 /* ... and that took the bf16x1 3x3 form (FRTM_WLAYOUT_BF16X1_3X3, csrc/conv3x3_bf16x1.hip): a counter of its own, the 1x1 counter does not move. */
 long frtm_conv_bf16x1_3x3_launches(void);
+/* ... and that took the bf16x1 3x3 stride-2 form (FRTM_WLAYOUT_BF16X1_3X3_S2, csrc/conv3x3s2_bf16x1.hip): its own counter again, the layout-7 one does not move. */
+long frtm_conv_bf16x1_3x3s2_launches(void);
 /* Host-side check of the multiplication the conv kernels use instead of integer divisions in their index arithmetic (csrc/conv_common.h: FastDiv,
  * q = (mulhi(n, m) + n) >> s with m, s prepared per divisor): returns n / d as that formula computes it, for 0 <= n < 2^31, d >= 1.
  * No GPU involved; tests/test_cpu_host.py sweeps it against Python's integer division. */
@@ -444,6 +451,13 @@ int frtm_backbone_set_precision(frtm_backbone_t* bb, int mode);
  * changes.  A per-conv plan keeps its conv on the fp32 path.  Environment FRTM_BF16X1_MIN_COLS=n (read at frtm_backbone_create; for tests and
  * measurements on small frames): every eligible conv of a bf16x1 trunk is routed from n columns per launch on, instead of the measured table. */
 int frtm_backbone_set_bf16_pieces(frtm_backbone_t* bb, int pieces);
+/* The 3x3 convs of a bf16x1 trunk on bf16 MFMAs as well (the bf16x1_3x3 trunk mode): on = 1 / 0; anything else is FRTM_ERR_ARG and leaves the state as
+ * it was.  The flag is stored independently of the pieces mode and takes effect only while that mode is 1 (bf16x1): then a 3x3 pad-1 conv of stride 1
+ * runs as FRTM_WLAYOUT_BF16X1_3X3 and one of stride 2 as FRTM_WLAYOUT_BF16X1_3X3_S2, where the 3x3 router picks it (csrc/backbone.hip: kBf16x1Rules3x3,
+ * profiles/bf16x1_trunk3x3_time.txt; under FRTM_BF16X1_MIN_COLS=n every such conv from n columns per launch on) and the conv has no per-conv plan.  The
+ * stem and the 1x1 convs are handled as without the flag.  Images are packed when the flag first turns on (and again by a later
+ * frtm_backbone_set_conv): for every 3x3 conv of ResNet-101 about 43 MB of device memory.  Bumps the generation when the flag's value changes. */
+int frtm_backbone_set_bf16x1_3x3(frtm_backbone_t* bb, int on);
 
 /* ------------------------------------------------------------------------------------------
  * Tracker.track mask merge (model/tracker.py:214-221), in place on masks (n_obj+1, H*W).
