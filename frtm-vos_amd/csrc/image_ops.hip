@@ -140,6 +140,7 @@ extern "C" int frtm_warp_mask_batch(const float* src, int Hs, int Ws, unsigned c
 // step takes ~100 ms whenever a blur size shows up for the first time, in the middle of a timed sequence).
 // One 16x16 output tile per block; the (16+kh-1) x (16+kw-1) input patch and G sit in LDS.
 #define BL_T 16
+#define BL_STATIC_LDS (16 * sizeof(float))          // red[16] of k_blur2d: counts against the 64 KB of a launch like the dynamic bytes
 // G == nullptr: the kernel is the normalised anisotropic Gaussian exp(-(qa x^2 + 2 qb x y + qc y^2) / 2), x = j - kw/2,
 // y = i - kh/2, built here from its three numbers -- nothing to upload from the host.
 __global__ __launch_bounds__(256) void k_blur2d(const float* __restrict__ src, int H, int W, const float* __restrict__ G, int kh, int kw,
@@ -182,7 +183,7 @@ __global__ __launch_bounds__(256) void k_blur2d(const float* __restrict__ src, i
 extern "C" int frtm_blur2d(const float* src, int planes, int H, int W, const float* G, int kh, int kw, float* dst, frtm_stream_t stream) {
   FRTM_CHECK_ARG(src && dst && G && planes > 0 && H > 0 && W > 0 && kh > 0 && kw > 0 && (kh & 1) && (kw & 1), "frtm_blur2d: bad argument (odd kernel sizes only)");
   const size_t lds = ((size_t)(BL_T + kh - 1) * (BL_T + kw - 1) + (size_t)kh * kw) * sizeof(float);
-  FRTM_CHECK_ARG(lds <= 64 * 1024, "frtm_blur2d: %dx%d kernel too large for the LDS tile", kh, kw);
+  FRTM_CHECK_ARG(lds + BL_STATIC_LDS <= 64 * 1024, "frtm_blur2d: %dx%d kernel too large for the LDS tile", kh, kw);
   dim3 g(ceil_div(W, BL_T), ceil_div(H, BL_T), planes);
   k_blur2d<<<g, 256, lds, (hipStream_t)stream>>>(src, H, W, G, kh, kw, 0.f, 0.f, 0.f, dst);
   FRTM_LAUNCH_CHECK();
@@ -194,7 +195,7 @@ extern "C" int frtm_blur_gauss2d(const float* src, int planes, int H, int W, int
   FRTM_CHECK_ARG(src && dst && planes > 0 && H > 0 && W > 0 && half >= 0, "frtm_blur_gauss2d: bad argument");
   const int k = 2 * half + 1;
   const size_t lds = ((size_t)(BL_T + k - 1) * (BL_T + k - 1) + (size_t)k * k) * sizeof(float);
-  FRTM_CHECK_ARG(lds <= 64 * 1024, "frtm_blur_gauss2d: half width %d too large for the LDS tile", half);
+  FRTM_CHECK_ARG(lds + BL_STATIC_LDS <= 64 * 1024, "frtm_blur_gauss2d: half width %d too large for the LDS tile", half);
   dim3 g(ceil_div(W, BL_T), ceil_div(H, BL_T), planes);
   k_blur2d<<<g, 256, lds, (hipStream_t)stream>>>(src, H, W, nullptr, k, k, qa, qb, qc, dst);
   FRTM_LAUNCH_CHECK();
