@@ -9,23 +9,18 @@
 #include <cstdio>
 #include "frtm_common.h"
 #include "../../include/frtm_hip.h"
+#include "trunk_route.h"
 
-void frtm_conv_plan(int M, int Ntot, int nchunks, int vec1x1, int* tile, int* splitk);
+int frtm_bf16x3_pack(const float* src, int Cout, int Cin, int sm, int sk, float* out, hipStream_t st);
+int frtm_bf16x1_pack(const float* src, int Cout, int Cin, int sm, int sk, float* out, hipStream_t st);
 
-struct ConvL {
-  int Cout, Cin, ks, stride, pad;
-  float* wT = nullptr; float* scale = nullptr; float* shift = nullptr; int* ktab = nullptr;
-  float* wW = nullptr;          // 3x3 stride-1 convs: second image of the weights, Winograd F(2x2,3x3) (FRTM_WLAYOUT_WINO3X3)
-  float* wW4 = nullptr;         // ... with >= 128 channels: third image, the 36 matrices of Winograd F(4x4,3x3) (FRTM_WLAYOUT_WINO4)
-  float* wW6 = nullptr;         // ... and the 64 matrices of F(6x6,3x3) (FRTM_WLAYOUT_WINO6)
-  float* wB = nullptr;          // convs a bf16x3 trunk routes (bf16x3_packs), bf16x3 trunks only: the three bf16 pieces (FRTM_WLAYOUT_BF16X3), packed lazily
-  float* wB1 = nullptr;         // convs a bf16x1 trunk routes (bf16x1_packs), bf16x1 trunks only: one bf16 plane (FRTM_WLAYOUT_BF16X1), packed lazily
-  float* wB3 = nullptr;         // 3x3 convs a bf16x1_3x3 trunk routes (bf16x1_3x3_packs): the bf16 image of FRTM_WLAYOUT_BF16X1_3X3 (stride 1) / _S2 (stride 2), packed lazily
+struct ConvL : TrunkConv {
+  // the weights, one image per kernel form the conv can take, indexed by FRTM_WLAYOUT_* (csrc/trunk_route.h: wanted_images says which exist; the
+  // bf16 ones are packed lazily, when their mode first turns on)
+  float* image[FRTM_WLAYOUT_BF16X1_3X3_S2 + 1] = {};
+  float* scale = nullptr; float* shift = nullptr; int* ktab = nullptr;
   bool loaded = false;
-  int layout = 0;
-  // per-conv launch plan (frtm_backbone_set_conv_plan; 0 = the planner's choice): the GEMM tile of the path the conv takes (direct 1x1 /
-  // gather conv, or the batched products of the three-launch Winograd forms; the output block 1..3 of the fused F(2x2,3x3) kernel) and split-K
-  int plan_tile = 0, plan_splitk = 0;
+  unsigned have() const { unsigned h = 0; for (int l = 0; l <= FRTM_WLAYOUT_BF16X1_3X3_S2; ++l) h |= (image[l] != nullptr) << l; return h; }
 };
 struct BlockL { int conv[3]; int nconv; int ds; };   // conv indices (ds = -1: identity shortcut)
 
@@ -53,15 +48,12 @@ struct frtm_backbone {
   double last_flops_form[4] = {0.0, 0.0, 0.0, 0.0};   // algorithmic FLOPs of the last pass by kernel form: direct, Winograd F(2x2,3x3), F(4x4,3x3), F(6x6,3x3)
   double last_flops_exec = 0.0;    // the same with Winograd launches counted at the MACs they execute (F(2x2,3x3): 16 per 2x2 outputs instead of 36; F(4x4,3x3): 36 per 4x4 tile instead of 144, partial edge tiles included)
   int last_launches = 0;
-  bool use_winograd = true;
-  // three-launch Winograd where it is eligible (run_conv): 0 = off, 1 = F(4x4,3x3) only, 2 = F(4x4,3x3) or F(6x6,3x3), whichever has fewer products
-  int use_winograd4 = getenv("FRTM_NO_WINO4") ? 0 : getenv("FRTM_NO_WINO6") ? 1 : 2;
-  // fewest 64x64 product tiles for which the three-launch forms are taken (256 = one per CU: measured at batch 1 -- the streaming path -- 2.49 -> 2.23 ms per trunk pass; FRTM_WINO4_MIN_TILES)
-  int wino4_min_tiles = getenv("FRTM_WINO4_MIN_TILES") ? atoi(getenv("FRTM_WINO4_MIN_TILES")) : 256;
-  int precision = 0;           // frtm_backbone_set_precision / _set_bf16_pieces: 0 = fp32, 1 = bf16x3 for the routed stride-1 1x1 convs (bf16x3_route), 2 = bf16x1 (bf16x1_route)
-  // FRTM_BF16X1_MIN_COLS=n (tests and measurements on small frames): a bf16x1 trunk routes EVERY eligible conv from n columns per launch on, instead of the measured table
-  int bf16x1_min_cols = getenv("FRTM_BF16X1_MIN_COLS") ? atoi(getenv("FRTM_BF16X1_MIN_COLS")) : -1;
-  bool bf16x1_3x3 = false;     // frtm_backbone_set_bf16x1_3x3: with precision == 2, the routed 3x3 convs on bf16 MFMAs as well (bf16x1_3x3_route); stored whatever the precision is
+  TrunkModes modes;            // the switches csrc/trunk_route.h decides by; the environment is read here, when the handle is created
+  frtm_backbone() {
+    modes.winograd4 = getenv("FRTM_NO_WINO4") ? 0 : getenv("FRTM_NO_WINO6") ? 1 : 2;
+    if (getenv("FRTM_WINO4_MIN_TILES")) modes.wino4_min_tiles = atoi(getenv("FRTM_WINO4_MIN_TILES"));
+    if (getenv("FRTM_BF16X1_MIN_COLS")) modes.bf16x1_min_cols = atoi(getenv("FRTM_BF16X1_MIN_COLS"));
+  }
   int generation = 0;          // bumped whenever an arena / workspace is (re)allocated: captured graphs of older generations are stale
 };
 
@@ -167,109 +159,6 @@ static int ensure(frtm_backbone* bb, float** p, size_t* have, size_t need) {
   return FRTM_OK;
 }
 
-// The planner's exceptions from the IN-TRUNK tile scan (tools/trunk_tile_scan.py, profiles/r04_trunk_tile_scan.txt: every candidate tile
-// of every conv class timed as a whole RN101 pass with the tracker's lanes).  At 16 frames in two lanes NO class moves the pass by more
-// than the run-to-run noise (+0.2 % for the whole scanned plan: the concurrent lane fills the tails that separate the tiles when a launch
-// is timed alone, profiles/r03_g32p_bench.txt); at the 4-5 frames per lane of the first-frame pass the 32x32x2-MFMA kernel is ahead on the
-// two dominant layer3 GEMMs (9.08 -> 8.92 ms per 9-frame pass).
-// `products`: the launch is the batched GEMM of a three-launch Winograd form (the tile of a 3x3 conv's DIRECT form is never touched).
-static int scanned_tile(const ConvL& c, int B, int Ho, int Wo, bool products) {
-  // Round 5, the exception itself A/B-ed (three alternating runs on one box, tools/trunk_bench.py): 9 frames in two lanes (102 / 127 column tiles per lane)
-  // 8.98-9.03 ms with it against 9.09-9.25 without; 5 frames (51 / 76 tiles) 5.79-5.80 with against 5.69-5.72 without -> from 96 tiles on only.
-  const long ntiles = ((long)B * Ho * Wo + 63) / 64;
-  if (ntiles < 96 || ntiles > 130 || c.Cin != 256) return 0;
-  if (products) return (c.ks == 3 && c.stride == 1 && c.Cout == 256) ? FRTM_TILE_G32_64x64 : 0;            // (tile counts are padded to 64)
-  if (c.ks == 1 && c.stride == 1 && c.Cout == 1024 && ((long)Ho * Wo) % 4 == 0) return FRTM_TILE_G32_64x64;  // (dwordx4 staging needs H*W % 4 == 0)
-  return 0;
-}
-
-int frtm_bf16x3_pack(const float* src, int Cout, int Cin, int sm, int sk, float* out, hipStream_t st);
-
-static bool bf16x3_eligible(const ConvL& c) { return c.ks == 1 && c.stride == 1 && c.pad == 0 && c.Cin % 16 == 0; }
-
-// The convs a bf16x3 trunk sends to the bf16x3 kernel: only where it measured faster than the fp32 form (DESIGN.md section 4,
-// profiles/bf16x3_trunk_time.txt): layer4's conv3 (512 -> 2048) with at least 3240 columns in the launch (8 frames of 480x854: 61 against 69 us).
-// Every other trunk 1x1 shape, and this one at 1 frame, measured slower (0.27-0.98x), so they stay fp32.
-static bool bf16x3_packs(const ConvL& c) { return bf16x3_eligible(c) && c.Cin == 512 && c.Cout == 2048; }
-static bool bf16x3_route(const ConvL& c, int B, int Ho, int Wo) { return bf16x3_packs(c) && (long)B * Ho * Wo >= 3240; }
-
-// the split image of an eligible conv from its packed GEMM image wT[Kp][Mp32] (w(m, k) = wT[k * Mp32 + m])
-static int pack_bf16x3(ConvL& c, hipStream_t st) {
-  if (!c.wB) FRTM_HIP(hipMalloc((void**)&c.wB, FRTM_CONV_BF16X3_ELEMS(c.Cout, c.Cin) * sizeof(float)));
-  return frtm_bf16x3_pack(c.wT, c.Cout, c.Cin, 1, (c.Cout + 31) / 32 * 32, c.wB, st);
-}
-
-int frtm_bf16x1_pack(const float* src, int Cout, int Cin, int sm, int sk, float* out, hipStream_t st);
-
-// The convs a bf16x1 trunk sends to the bf16x1 kernel (csrc/conv_bf16x1.hip): only where its median measured faster than the fp32 form the conv would
-// otherwise take by more than the spread (max - min over the alternating rounds) of the fp32 arm in the same run, per shape and columns of the launch
-// (tools/bf16x1_trunk_time.py -> profiles/bf16x1_trunk_time.txt, on 480x854 frames at 1 and 8 frames per launch).  A shape measured faster at 8
-// frames only is routed from its 8-frame column count on; one faster at 1 frame as well, from its 1-frame column count on.  Shapes that were not
-// measured (the conv1 of a stage's first block: 64 -> 64, 256 -> 128, 512 -> 256, 1024 -> 512), or were not faster, stay fp32.
-// us per launch, fp32 / bf16x1 (automatic tile form), from that file:            1 frame          8 frames
-struct Bf16x1Rule { int Cin, Cout; long min_cols; };
-static const Bf16x1Rule kBf16x1Rules[] = {
-  {256, 1024, 1620},      // layer3 conv3, 30x54                                  13.3 / 10.0      58.6 / 41.1
-  {1024, 256, 1620},      // layer3 conv1                                         18.8 / 15.1      67.5 / 24.7
-  {128, 512, 6420},       // layer2 conv3, 60x107                                 14.2 / 11.4      67.6 / 65.0
-  {512, 128, 6420},       // layer2 conv1                                         13.9 / 11.0      56.7 / 31.9
-  {512, 2048, 405},       // layer4 conv3, 15x27                                  20.4 / 11.6      71.9 / 33.3
-  {2048, 512, 3240},      // layer4 conv1: slower at 1 frame                      22.3 / 27.6      92.3 / 33.6
-  {256, 64, 25680},       // layer1 conv1, 120x214                                13.2 /  9.7      59.8 / 48.1
-  // 64 -> 256 (layer1 conv3 and downsample, K = 64: one chunk, nothing to pipeline)  14.2 / 17.2     114.7 / 139.1: stays fp32
-};
-static const Bf16x1Rule* bf16x1_rule(const ConvL& c) {
-  for (const Bf16x1Rule& r : kBf16x1Rules)
-    if (r.Cin == c.Cin && r.Cout == c.Cout) return &r;
-  return nullptr;
-}
-static bool bf16x1_packs(const frtm_backbone* bb, const ConvL& c) { return bf16x3_eligible(c) && (bb->bf16x1_min_cols >= 0 || bf16x1_rule(c)); }
-static bool bf16x1_route(const frtm_backbone* bb, const ConvL& c, int B, int Ho, int Wo) {
-  if (!bf16x1_packs(bb, c)) return false;
-  const long cols = (long)B * Ho * Wo;
-  return cols >= (bb->bf16x1_min_cols >= 0 ? (long)bb->bf16x1_min_cols : bf16x1_rule(c)->min_cols);
-}
-
-static int pack_bf16x1(ConvL& c, hipStream_t st) {
-  if (!c.wB1) FRTM_HIP(hipMalloc((void**)&c.wB1, FRTM_CONV_BF16X1_ELEMS(c.Cout, c.Cin) * sizeof(float)));
-  return frtm_bf16x1_pack(c.wT, c.Cout, c.Cin, 1, (c.Cout + 31) / 32 * 32, c.wB1, st);
-}
-
-// The 3x3 pad-1 convs a bf16x1_3x3 trunk (frtm_backbone_set_bf16x1_3x3 on top of bf16x1) sends to the direct bf16 kernels -- stride 1 to
-// FRTM_WLAYOUT_BF16X1_3X3 (csrc/conv3x3_bf16x1.hip), stride 2 to FRTM_WLAYOUT_BF16X1_3X3_S2 (csrc/conv3x3s2_bf16x1.hip) -- by the rule of kBf16x1Rules:
-// a shape is routed from the column count at which its median beat the fp32 form the conv otherwise takes (Winograd F(6x6) / F(4x4) / F(2x2), or the
-// halo kernel for stride 2) by more than the fp32 arm's max - min, at 1 and at 8 frames of 480x854 (tools/bf16x1_trunk3x3_time.py ->
-// profiles/bf16x1_trunk3x3_time.txt).  A shape faster at 8 frames only is routed from its 8-frame column count on, one faster at 1 frame as well from its
-// 1-frame column count on.  Shapes that were not measured, or were not faster, stay fp32.  The images are packed when the flag first turns on:
-// bf16 [Cin/16][9][2][Mp][8], 18 Cin Cout bytes per conv -- every 3x3 conv of ResNet-101 (3 x 64^2 + 4 x 128^2 + 23 x 256^2 + 3 x 512^2 weights x 18 B)
-// comes to about 43 MB of device memory; only the convs the table (or FRTM_BF16X1_MIN_COLS) can route are packed.
-// us per launch, fp32 form / bf16 (automatic tile form), from that file:                    1 frame          8 frames
-struct Bf16x1Rule3x3 { int Cin, Cout, stride; long min_cols; };
-static const Bf16x1Rule3x3 kBf16x1Rules3x3[] = {
-  {64, 64, 1, 25680},     // layer1, 120x214, fused F(2x2)                                    15.2 / 11.3      77.2 / 30.2
-  {128, 128, 1, 6420},    // layer2, 60x107, F(6x6)                                           24.0 / 16.7      70.8 / 23.5
-  {256, 256, 1, 12960},   // layer3, 30x54, F(6x6): slower at 1 frame                         22.0 / 28.4      57.3 / 30.4
-  {512, 512, 1, 3240},    // layer4, 15x27, F(4x4): slower at 1 frame                         31.1 / 50.6      62.4 / 51.6
-  {128, 128, 2, 6420},    // ResNet-50 / 101 layer2 opener, -> 60x107, halo                   40.2 / 31.5     193.8 / 52.1
-  {256, 256, 2, 12960},   // ... layer3 opener, -> 30x54: slower at 1 frame                   45.3 / 56.7     203.0 / 58.0
-  {512, 512, 2, 3240},    // ... layer4 opener, -> 15x27: slower at 1 frame                   49.7 / 101.7    201.0 / 102.1
-  {64, 128, 2, 6420},     // ResNet-18 / 34 layer2 opener, -> 60x107, halo                    30.5 / 18.3     105.2 / 29.8
-  {128, 256, 2, 1620},    // ... layer3 opener, -> 30x54                                      31.8 / 30.8     107.1 / 32.3
-  {256, 512, 2, 3240},    // ... layer4 opener, -> 15x27: slower at 1 frame                   34.4 / 53.2     103.6 / 53.9
-};
-static const Bf16x1Rule3x3* bf16x1_3x3_rule(const ConvL& c) {
-  for (const Bf16x1Rule3x3& r : kBf16x1Rules3x3)
-    if (r.Cin == c.Cin && r.Cout == c.Cout && r.stride == c.stride) return &r;
-  return nullptr;
-}
-static bool bf16x1_3x3_eligible(const ConvL& c) { return c.ks == 3 && c.pad == 1 && (c.stride == 1 || c.stride == 2); }
-static bool bf16x1_3x3_packs(const frtm_backbone* bb, const ConvL& c) { return bf16x1_3x3_eligible(c) && (bb->bf16x1_min_cols >= 0 || bf16x1_3x3_rule(c)); }
-static bool bf16x1_3x3_route(const frtm_backbone* bb, const ConvL& c, int B, int Ho, int Wo) {
-  if (!bf16x1_3x3_packs(bb, c)) return false;
-  const long cols = (long)B * Ho * Wo;
-  return cols >= (bb->bf16x1_min_cols >= 0 ? (long)bb->bf16x1_min_cols : bf16x1_3x3_rule(c)->min_cols);
-}
-
 // the halo image of a 3x3 conv (k_pack_weights_halo: wT[((ci / 8 * 9 + tap) * 8 + ci % 8) * Mp32 + m], exact fp32) back to OIHW
 __global__ __launch_bounds__(256) void k_halo_to_oihw(const float* __restrict__ wT, int Cout, int Cin, int Mp, float* __restrict__ w) {
   const size_t total = (size_t)Cout * Cin * 9;
@@ -279,21 +168,66 @@ __global__ __launch_bounds__(256) void k_halo_to_oihw(const float* __restrict__ 
   }
 }
 
-// the bf16 3x3 image of an eligible conv, from its OIHW weights (frtm_backbone_set_conv) or, w_oihw == nullptr, from its halo image
-static int pack_bf16x1_3x3(ConvL& c, const float* w_oihw, hipStream_t st) {
-  if (!c.wB3) FRTM_HIP(hipMalloc((void**)&c.wB3, FRTM_CONV_BF16X1_3X3_ELEMS(c.Cout, c.Cin) * sizeof(float)));
-  const int layout = c.stride == 2 ? FRTM_WLAYOUT_BF16X1_3X3_S2 : FRTM_WLAYOUT_BF16X1_3X3;
-  if (w_oihw) return frtm_conv_pack_weights(w_oihw, c.Cout, c.Cin, 3, layout, c.wB3, nullptr, (frtm_stream_t)st);
+static size_t image_elems(const ConvL& c, int layout) {
+  switch (layout) {
+    case FRTM_WLAYOUT_WINO3X3: return FRTM_CONV_WINO_ELEMS(c.Cout, c.Cin);
+    case FRTM_WLAYOUT_WINO4: return FRTM_CONV_WINO4_ELEMS(c.Cout, c.Cin);
+    case FRTM_WLAYOUT_WINO6: return FRTM_CONV_WINO6_ELEMS(c.Cout, c.Cin);
+    case FRTM_WLAYOUT_BF16X3: return FRTM_CONV_BF16X3_ELEMS(c.Cout, c.Cin);
+    case FRTM_WLAYOUT_BF16X1: return FRTM_CONV_BF16X1_ELEMS(c.Cout, c.Cin);
+    case FRTM_WLAYOUT_BF16X1_3X3: case FRTM_WLAYOUT_BF16X1_3X3_S2: return FRTM_CONV_BF16X1_3X3_ELEMS(c.Cout, c.Cin);
+    default: return FRTM_CONV_PACKED_ELEMS(c.Cout, c.Cin, c.ks);
+  }
+}
+
+// One image of a conv's weights, allocated at its first pack: from the OIHW weights (frtm_backbone_set_conv) or, w_oihw == nullptr (a mode that
+// turns on after the upload), from the image of the direct form, which holds them exactly.
+static int pack_image(ConvL& c, int layout, const float* w_oihw, hipStream_t st) {
+  float*& img = c.image[layout];
+  if (!img) FRTM_HIP(hipMalloc((void**)&img, image_elems(c, layout) * sizeof(float)));
+  const int base = base_layout(c), Mp32 = (c.Cout + 31) / 32 * 32;
+  // the 1x1 bf16 images: split / rounded from the packed GEMM image wT[Kp][Mp32] (w(m, k) = wT[k * Mp32 + m])
+  if (layout == FRTM_WLAYOUT_BF16X3) return frtm_bf16x3_pack(c.image[base], c.Cout, c.Cin, 1, Mp32, img, st);
+  if (layout == FRTM_WLAYOUT_BF16X1) return frtm_bf16x1_pack(c.image[base], c.Cout, c.Cin, 1, Mp32, img, st);
+  if (w_oihw) return frtm_conv_pack_weights(w_oihw, c.Cout, c.Cin, c.ks, layout, img, layout == base ? c.ktab : nullptr, (frtm_stream_t)st);
   float* tmp = nullptr;
   const size_t total = (size_t)c.Cout * c.Cin * 9;
   FRTM_HIP(hipMalloc((void**)&tmp, total * sizeof(float)));
-  k_halo_to_oihw<<<(int)std::min<size_t>((total + 255) / 256, 2048), 256, 0, st>>>(c.wT, c.Cout, c.Cin, (c.Cout + 31) / 32 * 32, tmp);
+  k_halo_to_oihw<<<(int)std::min<size_t>((total + 255) / 256, 2048), 256, 0, st>>>(c.image[FRTM_WLAYOUT_HALO3X3], c.Cout, c.Cin, Mp32, tmp);
   int rc = FRTM_ERR_HIP;
-  if (hipGetLastError() == hipSuccess) rc = frtm_conv_pack_weights(tmp, c.Cout, c.Cin, 3, layout, c.wB3, nullptr, (frtm_stream_t)st);
+  if (hipGetLastError() == hipSuccess) rc = frtm_conv_pack_weights(tmp, c.Cout, c.Cin, 3, layout, img, nullptr, (frtm_stream_t)st);
   else frtm_set_error("backbone: k_halo_to_oihw failed to launch");
   (void)hipStreamSynchronize(st);           // the temporary dies here
   (void)hipFree(tmp);
   return rc;
+}
+
+// Packs the images that the modes `next` want and the loaded convs do not hold yet.  A configuration call, not a stream operation: the images of
+// the direct form may come from any stream, and the new ones are ready on return.
+static int pack_missing(frtm_backbone* bb, const TrunkModes& next) {
+  bool synced = false;
+  for (auto& c : bb->convs)
+    for (int l = 0; c.loaded && l <= FRTM_WLAYOUT_BF16X1_3X3_S2; ++l)
+      if ((wanted_images(next, c) & ~c.have()) >> l & 1) {
+        if (!synced) FRTM_HIP(hipDeviceSynchronize());
+        synced = true;
+        int rc = pack_image(c, l, nullptr, nullptr);
+        if (rc) return rc;
+      }
+  if (synced) FRTM_HIP(hipDeviceSynchronize());
+  return FRTM_OK;
+}
+
+// A precision switch (TrunkModes::precision and ::bf16x1_3x3): the images first (a failure leaves the modes as they were), then the modes
+static int set_modes(frtm_backbone* bb, int precision, bool bf16x1_3x3) {
+  TrunkModes next = bb->modes;
+  next.precision = precision;
+  next.bf16x1_3x3 = bf16x1_3x3;
+  int rc = pack_missing(bb, next);
+  if (rc) return rc;
+  if (next.precision != bb->modes.precision || next.bf16x1_3x3 != bb->modes.bf16x1_3x3) bb->generation += 1;       // captured graphs hold the other kernels
+  bb->modes = next;
+  return FRTM_OK;
 }
 
 static int run_conv(frtm_backbone* bb, Lane& ln, int idx, int B, int Hin, int Win, const float* in, const float* residual, int relu,
@@ -301,11 +235,8 @@ static int run_conv(frtm_backbone* bb, Lane& ln, int idx, int B, int Hin, int Wi
   ConvL& c = bb->convs[idx];
   if (!c.loaded) { frtm_set_error("backbone: conv %d has no weights (call frtm_backbone_set_conv)", idx); return FRTM_ERR_STATE; }
   const int pad = pad_override >= 0 ? pad_override : c.pad;   // (the stem runs on an image whose border the normalisation kernel has written)
-  frtm_conv_desc d;
-  d.B = B; d.Cin = c.Cin; d.Hin = Hin; d.Win = Win; d.Cout = c.Cout; d.ksize = c.ks; d.stride = c.stride; d.pad = pad;
-  d.relu = relu; d.out_transposed = 0; d.splitk = 0; d.tile = 0; d.w_pitch = 0; d.w_layout = c.layout; d.ws_elems = 0;
-  *Ho = (Hin + 2 * pad - c.ks) / c.stride + 1;
-  *Wo = (Win + 2 * pad - c.ks) / c.stride + 1;
+  *Ho = conv_out_dim(c, Hin, pad);
+  *Wo = conv_out_dim(c, Win, pad);
   // conv2d plans tile/split-K itself; the workspace must cover the largest split it can pick.  Split-K is only
   // chosen when the launch has < ~800 workgroups, i.e. Cout*N <= ~800*64*64 elements, so bound it by that.
   {
@@ -314,72 +245,22 @@ static int run_conv(frtm_backbone* bb, Lane& ln, int idx, int B, int Hin, int Wi
     int rc = ensure(bb, &ln.ws, &ln.ws_elems, std::max(w, out_elems * 2));
     if (rc) return rc;
   }
-  d.ws_elems = (int)std::min<size_t>(ln.ws_elems, 0x7fffffff);
+  const Route r = choose_route(bb->modes, c, B, *Ho, *Wo, pad, c.have());
+  if (r.ws4_elems) {
+    int rc = ensure(bb, &ln.ws4, &ln.ws4_elems, r.ws4_elems);
+    if (rc) return rc;
+  }
   bb->last_launches += 1;
-  bb->last_flops += 2.0 * c.Cout * (double)B * (*Ho) * (*Wo) * c.Cin * c.ks * c.ks;      // algorithmic (direct-form) FLOPs
-  // bf16x1_3x3 trunks: the routed 3x3 convs on bf16 MFMAs (direct form: full MACs), before any Winograd form is considered
-  if (bb->precision == 2 && bb->bf16x1_3x3 && c.wB3 && pad == 1 && !c.plan_tile && !c.plan_splitk && bf16x1_3x3_route(bb, c, B, *Ho, *Wo)) {
-    d.w_layout = c.stride == 2 ? FRTM_WLAYOUT_BF16X1_3X3_S2 : FRTM_WLAYOUT_BF16X1_3X3;
-    d.splitk = 1;
-    bb->last_flops_exec += 2.0 * c.Cout * (double)B * (*Ho) * (*Wo) * c.Cin * 9.0;
-    bb->last_flops_form[0] += 2.0 * c.Cout * (double)B * (*Ho) * (*Wo) * c.Cin * 9.0;
-    return frtm_conv2d(&d, in, c.wB3, nullptr, c.scale, c.shift, residual, out, nullptr, st);
-  }
-  // Winograd F(4x4,3x3) / F(6x6,3x3), three-launch form (conv_wino4.hip), for the wide 3x3 stride-1 convs: 2.25 / 1.78 multiplications
-  // per output instead of 4; eligible when the products fill the chip as one GEMM launch and the output tiles waste < 25 % on the
-  // map's edges; of the two, the form with fewer products = (m+2)^2 x padded tile count (30x54: 6x6 tiles fit exactly, 64 x 384 against
-  // 36 x 896 at 8 frames).  Measured at 8 frames (tools/wino4_bench.py): 256 ch 30x54 62 (F6) / 69 (F4) vs 100 us fused F(2x2), 512 ch
-  // 15x27 58 / 68 vs 105, 128 ch 60x107 76 / 85 vs 101; 64 ch 120x214 is slower (128 / 145 vs 108: K = 64 GEMMs, transform traffic).
-  if (c.wW4 && bb->use_winograd && bb->use_winograd4) {
-    int best_m = 0; long best_cost = 0, best_T = 0, best_Tp = 0;
-    for (int m : {6, 4}) {
-      if (m == 6 && (bb->use_winograd4 < 2 || !c.wW6)) continue;
-      const int th = ceil_div(*Ho, m), tw = ceil_div(*Wo, m), NP = (m + 2) * (m + 2);
-      const long T = (long)B * th * tw, Tp = (T + 63) / 64 * 64;
-      if ((long)ceil_div(c.Cout, 64) * (NP * Tp / 64) < bb->wino4_min_tiles || (long)m * m * th * tw * 4 > (long)5 * (*Ho) * (*Wo) ||
-          (size_t)NP * std::max(c.Cin, c.Cout) * Tp * 4 >= 0x7fffffffull)       // (32-bit buffer offsets of the transformed tensors)
-        continue;
-      if (!best_m || NP * Tp < best_cost) { best_m = m; best_cost = NP * Tp; best_T = T; best_Tp = Tp; }
-    }
-    if (best_m) {
-      const int NP = (best_m + 2) * (best_m + 2);
-      const size_t need = (size_t)NP * (c.Cin + c.Cout) * best_Tp;
-      int rc = ensure(bb, &ln.ws4, &ln.ws4_elems, need);
-      if (rc) return rc;
-      d.w_layout = best_m == 6 ? FRTM_WLAYOUT_WINO6 : FRTM_WLAYOUT_WINO4;
-      d.splitk = 1;
-      d.tile = c.plan_tile ? c.plan_tile : scanned_tile(c, B, *Ho, *Wo, true);
-      d.ws_elems = (int)std::min<size_t>(ln.ws4_elems, 0x7fffffff);
-      bb->last_flops_exec += 2.0 * c.Cout * (double)c.Cin * NP * (double)best_T;
-      bb->last_flops_form[best_m == 6 ? 3 : 2] += 2.0 * c.Cout * (double)B * (*Ho) * (*Wo) * c.Cin * 9.0;
-      return frtm_conv2d(&d, in, best_m == 6 ? c.wW6 : c.wW4, nullptr, c.scale, c.shift, residual, out, ln.ws4, st);
-    }
-  }
-  // Winograd for the 3x3 stride-1 convs whenever the launch has enough 8x8 output blocks to fill the chip without split-K
-  if (c.wW && bb->use_winograd &&
-      (long)B * ceil_div(*Ho, 8) * ceil_div(*Wo, 8) * ceil_div(c.Cout, 32) >= FRTM_WINO_MIN_BLOCKS) {
-    d.w_layout = FRTM_WLAYOUT_WINO3X3;
-    d.splitk = 1;
-    d.tile = (c.plan_tile >= 1 && c.plan_tile <= 3) ? c.plan_tile : 0;
-    bb->last_flops_exec += 2.0 * c.Cout * (double)B * (*Ho) * (*Wo) * c.Cin * c.ks * c.ks * (16.0 / 36.0);
-    bb->last_flops_form[1] += 2.0 * c.Cout * (double)B * (*Ho) * (*Wo) * c.Cin * 9.0;
-    return frtm_conv2d(&d, in, c.wW, nullptr, c.scale, c.shift, residual, out, ln.ws, st);
-  }
-  bb->last_flops_exec += 2.0 * c.Cout * (double)B * (*Ho) * (*Wo) * c.Cin * c.ks * c.ks;
-  bb->last_flops_form[0] += 2.0 * c.Cout * (double)B * (*Ho) * (*Wo) * c.Cin * c.ks * c.ks;
-  if (bb->precision == 1 && c.wB && !c.plan_tile && !c.plan_splitk && bf16x3_route(c, B, *Ho, *Wo)) {
-    d.w_layout = FRTM_WLAYOUT_BF16X3;
-    d.splitk = 1;
-    return frtm_conv2d(&d, in, c.wB, nullptr, c.scale, c.shift, residual, out, nullptr, st);
-  }
-  if (bb->precision == 2 && c.wB1 && !c.plan_tile && !c.plan_splitk && bf16x1_route(bb, c, B, *Ho, *Wo)) {
-    d.w_layout = FRTM_WLAYOUT_BF16X1;
-    d.splitk = 1;
-    return frtm_conv2d(&d, in, c.wB1, nullptr, c.scale, c.shift, residual, out, nullptr, st);
-  }
-  d.tile = c.plan_tile ? c.plan_tile : scanned_tile(c, B, *Ho, *Wo, false);
-  d.splitk = c.plan_splitk;
-  return frtm_conv2d(&d, in, c.wT, c.ktab, c.scale, c.shift, residual, out, ln.ws, st);
+  bb->last_flops += direct_flops(c, B, *Ho, *Wo);
+  bb->last_flops_form[r.flops_slot] += direct_flops(c, B, *Ho, *Wo);
+  bb->last_flops_exec += r.exec_flops;
+  frtm_conv_desc d;
+  d.B = B; d.Cin = c.Cin; d.Hin = Hin; d.Win = Win; d.Cout = c.Cout; d.ksize = c.ks; d.stride = c.stride; d.pad = pad;
+  d.relu = relu; d.out_transposed = 0; d.splitk = r.splitk; d.tile = r.tile; d.w_pitch = 0; d.w_layout = r.layout;
+  d.ws_elems = (int)std::min<size_t>(r.ws4_elems ? ln.ws4_elems : ln.ws_elems, 0x7fffffff);
+  // workspace: the transformed tensors of the three-launch forms, split-K partials / the fused F(2x2) kernel's scratch, none for the bf16 forms
+  float* ws = r.ws4_elems ? ln.ws4 : r.layout >= FRTM_WLAYOUT_BF16X3 ? nullptr : ln.ws;
+  return frtm_conv2d(&d, in, c.image[r.layout], r.layout == base_layout(c) ? c.ktab : nullptr, c.scale, c.shift, residual, out, ws, st);
 }
 
 // One sub-batch through the trunk on one stream (reference feature_extractor.py:40-68).
@@ -534,13 +415,7 @@ int frtm_backbone_create(int arch, frtm_backbone_t** out) {
 int frtm_backbone_destroy(frtm_backbone_t* bb) {
   if (!bb) return FRTM_OK;
   for (auto& c : bb->convs) {
-    if (c.wT) (void)hipFree(c.wT);
-    if (c.wW) (void)hipFree(c.wW);
-    if (c.wW4) (void)hipFree(c.wW4);
-    if (c.wW6) (void)hipFree(c.wW6);
-    if (c.wB) (void)hipFree(c.wB);
-    if (c.wB1) (void)hipFree(c.wB1);
-    if (c.wB3) (void)hipFree(c.wB3);
+    for (float* img : c.image) if (img) (void)hipFree(img);
     if (c.scale) (void)hipFree(c.scale);
     if (c.shift) (void)hipFree(c.shift);
     if (c.ktab) (void)hipFree(c.ktab);
@@ -567,6 +442,15 @@ int frtm_backbone_conv_info(const frtm_backbone_t* bb, int idx, int* out6) {
   return FRTM_OK;
 }
 
+int frtm_backbone_conv_route(const frtm_backbone_t* bb, int idx, int B, int Hin, int Win, int* out3) {
+  FRTM_CHECK_ARG(bb && out3 && idx >= 0 && idx < (int)bb->convs.size(), "frtm_backbone_conv_route: bad index %d", idx);
+  const ConvL& c = bb->convs[idx];
+  FRTM_CHECK_ARG(B > 0 && Hin + 2 * c.pad >= c.ks && Win + 2 * c.pad >= c.ks, "frtm_backbone_conv_route: conv %d cannot run on %d images of %d x %d", idx, B, Hin, Win);
+  const Route r = choose_route(bb->modes, c, B, conv_out_dim(c, Hin, c.pad), conv_out_dim(c, Win, c.pad), c.pad, wanted_images(bb->modes, c));
+  out3[0] = r.layout; out3[1] = r.tile; out3[2] = r.flops_slot;
+  return FRTM_OK;
+}
+
 int frtm_backbone_set_conv_plan(frtm_backbone_t* bb, int idx, int tile, int splitk) {
   FRTM_CHECK_ARG(bb && idx >= 0 && idx < (int)bb->convs.size() && tile >= 0 && splitk >= 0, "frtm_backbone_set_conv_plan: bad argument");
   bb->convs[idx].plan_tile = tile;
@@ -579,42 +463,19 @@ int frtm_backbone_set_conv(frtm_backbone_t* bb, int idx, const float* w_oihw, co
                            frtm_stream_t stream) {
   FRTM_CHECK_ARG(bb && w_oihw && bn_scale && bn_shift && idx >= 0 && idx < (int)bb->convs.size(), "frtm_backbone_set_conv: bad argument");
   ConvL& c = bb->convs[idx];
-  const size_t K = (size_t)c.Cin * c.ks * c.ks;
   hipStream_t st = (hipStream_t)stream;
-  if (!c.wT) {
-    FRTM_HIP(hipMalloc((void**)&c.wT, (size_t)FRTM_CONV_PACKED_ELEMS(c.Cout, c.Cin, c.ks) * sizeof(float)));
+  if (!c.scale) {
     FRTM_HIP(hipMalloc((void**)&c.scale, c.Cout * sizeof(float)));
     FRTM_HIP(hipMalloc((void**)&c.shift, c.Cout * sizeof(float)));
-    if (c.ks > 1) FRTM_HIP(hipMalloc((void**)&c.ktab, K * 3 * sizeof(int)));
+    if (c.ks > 1) FRTM_HIP(hipMalloc((void**)&c.ktab, (size_t)c.Cin * c.ks * c.ks * 3 * sizeof(int)));
   }
-  c.layout = (c.ks == 3 && c.stride <= 2 && c.pad == 1) ? FRTM_WLAYOUT_HALO3X3 : FRTM_WLAYOUT_GEMM;
-  int rc = frtm_conv_pack_weights(w_oihw, c.Cout, c.Cin, c.ks, c.layout, c.wT, c.ktab, stream);
-  if (rc) return rc;
-  if (bf16x3_packs(c) && (c.wB || bb->precision == 1)) {
-    rc = pack_bf16x3(c, st);
-    if (rc) return rc;
-  }
-  if (bf16x1_packs(bb, c) && (c.wB1 || bb->precision == 2)) {
-    rc = pack_bf16x1(c, st);
-    if (rc) return rc;
-  }
-  if (bf16x1_3x3_packs(bb, c) && (c.wB3 || bb->bf16x1_3x3)) {
-    rc = pack_bf16x1_3x3(c, w_oihw, st);
-    if (rc) return rc;
-  }
-  if (c.ks == 3 && c.stride == 1 && c.pad == 1) {
-    if (!c.wW) FRTM_HIP(hipMalloc((void**)&c.wW, (size_t)FRTM_CONV_WINO_ELEMS(c.Cout, c.Cin) * sizeof(float)));
-    rc = frtm_conv_pack_weights(w_oihw, c.Cout, c.Cin, 3, FRTM_WLAYOUT_WINO3X3, c.wW, nullptr, stream);
-    if (rc) return rc;
-    if (c.Cin >= 128 && c.Cin % 32 == 0 && c.Cout % 64 == 0) {
-      if (!c.wW4) FRTM_HIP(hipMalloc((void**)&c.wW4, (size_t)FRTM_CONV_WINO4_ELEMS(c.Cout, c.Cin) * sizeof(float)));
-      rc = frtm_conv_pack_weights(w_oihw, c.Cout, c.Cin, 3, FRTM_WLAYOUT_WINO4, c.wW4, nullptr, stream);
-      if (rc) return rc;
-      if (!c.wW6) FRTM_HIP(hipMalloc((void**)&c.wW6, (size_t)FRTM_CONV_WINO6_ELEMS(c.Cout, c.Cin) * sizeof(float)));
-      rc = frtm_conv_pack_weights(w_oihw, c.Cout, c.Cin, 3, FRTM_WLAYOUT_WINO6, c.wW6, nullptr, stream);
+  // every image the modes want, and every one the conv already holds; ascending: the direct form's image (0 / 1) first, the 1x1 bf16 images read it
+  const unsigned want = wanted_images(bb->modes, c, c.have());
+  for (int l = 0; l <= FRTM_WLAYOUT_BF16X1_3X3_S2; ++l)
+    if (want >> l & 1) {
+      int rc = pack_image(c, l, w_oihw, st);
       if (rc) return rc;
     }
-  }
   FRTM_HIP(hipMemcpyAsync(c.scale, bn_scale, c.Cout * sizeof(float), hipMemcpyDeviceToDevice, st));
   FRTM_HIP(hipMemcpyAsync(c.shift, bn_shift, c.Cout * sizeof(float), hipMemcpyDeviceToDevice, st));
   c.loaded = true;
@@ -628,66 +489,31 @@ int frtm_backbone_last_conv_launches(const frtm_backbone_t* bb) { return bb ? bb
 int frtm_backbone_generation(const frtm_backbone_t* bb) { return bb ? bb->generation : 0; }
 int frtm_backbone_set_winograd(frtm_backbone_t* bb, int enable) {
   FRTM_CHECK_ARG(bb, "frtm_backbone_set_winograd: null handle");
-  bb->use_winograd = enable != 0;
-  return FRTM_OK;
-}
-
-// mode: 0 = fp32, 1 = bf16x3, 2 = bf16x1 (the values of frtm_backbone::precision)
-static int set_precision_mode(frtm_backbone* bb, int mode) {
-  auto wants = [&](const ConvL& c) { return c.loaded && ((mode == 1 && bf16x3_packs(c) && !c.wB) || (mode == 2 && bf16x1_packs(bb, c) && !c.wB1)); };
-  bool pack = false;
-  for (auto& c : bb->convs) pack |= wants(c);
-  if (pack) {            // a configuration call, not a stream operation: the GEMM images may come from any stream, and the bf16 ones are ready on return
-    FRTM_HIP(hipDeviceSynchronize());
-    for (auto& c : bb->convs)
-      if (wants(c)) {
-        int rc = mode == 1 ? pack_bf16x3(c, nullptr) : pack_bf16x1(c, nullptr);
-        if (rc) return rc;
-      }
-    FRTM_HIP(hipDeviceSynchronize());
-  }
-  if (mode != bb->precision) bb->generation += 1;       // captured graphs hold the other kernels
-  bb->precision = mode;
+  bb->modes.winograd = enable != 0;
   return FRTM_OK;
 }
 
 int frtm_backbone_set_precision(frtm_backbone_t* bb, int mode) {
   FRTM_CHECK_ARG(bb, "frtm_backbone_set_precision: null handle");
   FRTM_CHECK_ARG(mode == 0 || mode == 1, "frtm_backbone_set_precision: mode must be 0 (fp32) or 1 (bf16x3), got %d", mode);
-  return set_precision_mode(bb, mode);
+  return set_modes(bb, mode, bb->modes.bf16x1_3x3);
 }
 
 int frtm_backbone_set_bf16_pieces(frtm_backbone_t* bb, int pieces) {
   FRTM_CHECK_ARG(bb, "frtm_backbone_set_bf16_pieces: null handle");
   FRTM_CHECK_ARG(pieces == 0 || pieces == 1 || pieces == 3, "frtm_backbone_set_bf16_pieces: pieces must be 0 (fp32), 1 (bf16x1) or 3 (bf16x3), got %d", pieces);
-  return set_precision_mode(bb, pieces == 3 ? 1 : pieces == 1 ? 2 : 0);
+  return set_modes(bb, pieces == 3 ? 1 : pieces == 1 ? 2 : 0, bb->modes.bf16x1_3x3);
 }
 
 int frtm_backbone_set_bf16x1_3x3(frtm_backbone_t* bb, int on) {
   FRTM_CHECK_ARG(bb, "frtm_backbone_set_bf16x1_3x3: null handle");
   FRTM_CHECK_ARG(on == 0 || on == 1, "frtm_backbone_set_bf16x1_3x3: on must be 0 or 1, got %d", on);
-  if (on) {
-    auto wants = [&](const ConvL& c) { return c.loaded && bf16x1_3x3_packs(bb, c) && !c.wB3; };
-    bool pack = false;
-    for (auto& c : bb->convs) pack |= wants(c);
-    if (pack) {          // a configuration call, as set_precision_mode: the halo images may come from any stream, the bf16 ones are ready on return
-      FRTM_HIP(hipDeviceSynchronize());
-      for (auto& c : bb->convs)
-        if (wants(c)) {
-          int rc = pack_bf16x1_3x3(c, nullptr, nullptr);
-          if (rc) return rc;
-        }
-      FRTM_HIP(hipDeviceSynchronize());
-    }
-  }
-  if ((on != 0) != bb->bf16x1_3x3) bb->generation += 1;       // captured graphs hold the other kernels
-  bb->bf16x1_3x3 = on != 0;
-  return FRTM_OK;
+  return set_modes(bb, bb->modes.precision, on != 0);
 }
 
 int frtm_backbone_set_winograd4(frtm_backbone_t* bb, int enable) {
   FRTM_CHECK_ARG(bb, "frtm_backbone_set_winograd4: null handle");
-  bb->use_winograd4 = enable < 0 ? 0 : enable > 2 ? 2 : enable;
+  bb->modes.winograd4 = enable < 0 ? 0 : enable > 2 ? 2 : enable;
   return FRTM_OK;
 }
 

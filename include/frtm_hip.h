@@ -361,6 +361,10 @@ int frtm_backbone_destroy(frtm_backbone_t* bb);
 int frtm_backbone_num_convs(const frtm_backbone_t* bb);
 /* Shape of conv #idx in forward order: out6 = {Cout, Cin, ksize, stride, pad, has_residual_input} */
 int frtm_backbone_conv_info(const frtm_backbone_t* bb, int idx, int* out6_host);
+/* The form conv #idx takes for B images of Hin x Win input (under its own padding: ask the stem at the frame size) with the handle's modes and
+ * plan as they are now: out3 = {FRTM_WLAYOUT_* of the launch, FRTM_TILE_* or 0, slot of frtm_backbone_last_flops_form}.  The decision of the
+ * forward pass itself (csrc/trunk_route.h: choose_route) for a conv whose weights are loaded; needs neither weights nor a device. */
+int frtm_backbone_conv_route(const frtm_backbone_t* bb, int idx, int B, int Hin, int Win, int* out3_host);
 /* Per-conv launch plan override (0 = the planner's choice): `tile` = FRTM_TILE_* of the GEMM launch of whichever path the conv takes (the
  * direct 1x1 / gather conv, the batched products of the three-launch Winograd forms) or the output block 1..3 of the fused F(2x2,3x3)
  * kernel; `splitk` as in frtm_conv_desc.  Used by tools/trunk_tile_scan.py to scan tiles IN the trunk (concurrent lanes change the
@@ -445,7 +449,7 @@ int frtm_backbone_set_winograd4(frtm_backbone_t* bb, int enable);
  * packed when mode 1 is first set (and again by a later frtm_backbone_set_conv); mode 0 allocates nothing.  Bumps the generation. */
 int frtm_backbone_set_precision(frtm_backbone_t* bb, int mode);
 /* The same switch by the number of bf16 pieces per operand: 0 = fp32, 3 = bf16x3 (identical to frtm_backbone_set_precision(bb, 1)), 1 = bf16x1 --
- * the stride-1 1x1 convs that the bf16x1 router picks (csrc/backbone.hip: bf16x1_route, profiles/bf16x1_trunk_time.txt) run as FRTM_WLAYOUT_BF16X1.
+ * the stride-1 1x1 convs that the bf16x1 router picks (csrc/trunk_route.h: kTrunkRules, profiles/bf16x1_trunk_time.txt) run as FRTM_WLAYOUT_BF16X1.
  * Anything else (2 included) is FRTM_ERR_ARG and leaves the mode as it was.  The two bf16 modes are exclusive: a bf16x1 trunk never launches the
  * bf16x3 kernel.  Images are packed when the mode is first set (and again by a later frtm_backbone_set_conv); bumps the generation when the mode
  * changes.  A per-conv plan keeps its conv on the fp32 path.  Environment FRTM_BF16X1_MIN_COLS=n (read at frtm_backbone_create; for tests and
@@ -453,7 +457,7 @@ int frtm_backbone_set_precision(frtm_backbone_t* bb, int mode);
 int frtm_backbone_set_bf16_pieces(frtm_backbone_t* bb, int pieces);
 /* The 3x3 convs of a bf16x1 trunk on bf16 MFMAs as well (the bf16x1_3x3 trunk mode): on = 1 / 0; anything else is FRTM_ERR_ARG and leaves the state as
  * it was.  The flag is stored independently of the pieces mode and takes effect only while that mode is 1 (bf16x1): then a 3x3 pad-1 conv of stride 1
- * runs as FRTM_WLAYOUT_BF16X1_3X3 and one of stride 2 as FRTM_WLAYOUT_BF16X1_3X3_S2, where the 3x3 router picks it (csrc/backbone.hip: kBf16x1Rules3x3,
+ * runs as FRTM_WLAYOUT_BF16X1_3X3 and one of stride 2 as FRTM_WLAYOUT_BF16X1_3X3_S2, where the 3x3 router picks it (csrc/trunk_route.h: kTrunkRules,
  * profiles/bf16x1_trunk3x3_time.txt; under FRTM_BF16X1_MIN_COLS=n every such conv from n columns per launch on) and the conv has no per-conv plan.  The
  * stem and the 1x1 convs are handled as without the flag.  Images are packed when the flag first turns on (and again by a later
  * frtm_backbone_set_conv): for every 3x3 conv of ResNet-101 about 43 MB of device memory.  Bumps the generation when the flag's value changes. */

@@ -308,7 +308,7 @@ def _with_min_cols(make, n=MIN_COLS):
 
 def routed_convs(ext, lane_frames, min_cols=MIN_COLS):
     """Indices of the convs a bf16x1 trunk created under FRTM_BF16X1_MIN_COLS sends to the bf16x1 kernel at `lane_frames` frames of 96x160 per lane
-    (backbone.hip: bf16x1_route): 1x1, stride 1, Cin % 16 == 0 and lane_frames x (pixels of the conv's map) >= min_cols.  Bottleneck trunks: conv3 and
+    (csrc/trunk_route.h: choose_route): 1x1, stride 1, Cin % 16 == 0 and lane_frames x (pixels of the conv's map) >= min_cols.  Bottleneck trunks: conv3 and
     layer1's downsample (Cout = 4 Cin) and the conv1 of later blocks (Cin = 4 Cout) run on their stage's map, the conv1 of a stage's first block
     (Cin = 2 Cout, or 64 -> 64) on the stage before's."""
     from frtm_vos_amd import _hip as H
@@ -439,7 +439,7 @@ def test_trunk_vs_oracle_is_printed_not_gated():
         assert bool(torch.isfinite(out['bf16x1'][k]).all()), k
 
 
-# (Cin, Cout) -> fewest columns per launch from which backbone.hip's kBf16x1Rules routes the shape (profiles/bf16x1_trunk_time.txt)
+# (Cin, Cout) -> fewest columns per launch from which trunk_route.h's kTrunkRules routes the shape (profiles/bf16x1_trunk_time.txt)
 DEFAULT_RULES = {(256, 1024): 1620, (1024, 256): 1620, (128, 512): 6420, (512, 128): 6420, (512, 2048): 405, (2048, 512): 3240, (256, 64): 25680}
 
 

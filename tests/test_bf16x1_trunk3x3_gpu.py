@@ -408,6 +408,63 @@ def test_trunk_routing_counts_round_trip_lanes_and_plan(name):
         ext.lanes = 1
 
 
+def conv_inputs(ext, H, W):
+    """[(idx, (Cout, Cin, k, stride, pad), (Hin, Win))] in forward order: the stem at the frame; per block conv1 [conv2] [conv3] [downsample], the
+    first block of stages 1..3 on the previous stage's map, which only its strided conv (the 3x3 of a bottleneck, conv1 of a BasicBlock) and its
+    downsample leave."""
+    from frtm_vos_amd import _hip as H_
+    info, shapes = (ctypes.c_int * 6)(), []
+    for i in range(_lib().frtm_backbone_num_convs(ext._handle)):
+        H_.call_nostream('frtm_backbone_conv_info', ext._handle, i, info)
+        shapes.append(tuple(info[:5]))
+    bott = hasattr(ext.resnet.layer1[0], 'conv3')
+    half = lambda hw: ((hw[0] + 1) // 2, (hw[1] + 1) // 2)          # noqa: E731
+    out, i, cur = [(0, shapes[0], (H, W))], 1, half(half((H, W)))
+    for s in range(4):
+        for b, blk in enumerate(getattr(ext.resnet, 'layer%d' % (s + 1))):
+            own = half(cur) if (s > 0 and b == 0) else cur
+            for j in range(3 if bott else 2):
+                out.append((i, shapes[i], cur if j <= (1 if bott else 0) else own))
+                i += 1
+            if hasattr(blk, 'downsample'):
+                out.append((i, shapes[i], cur))
+                i += 1
+            cur = own
+    assert i == len(shapes)
+    return out
+
+
+@pytest.mark.parametrize('name', ('resnet18', 'resnet50'))
+def test_the_pass_takes_the_routes_the_query_reports(name):
+    """frtm_backbone_conv_route decides from the modes alone (csrc/trunk_route.h: wanted_images); the pass decides from the images the convs really hold.
+    Per mode the launch counters of a pass and its four FLOP ledgers must be what the query says for every conv at its own input size."""
+    ext, img, _ = _trunk(name)
+    B = img.shape[0]
+    convs = conv_inputs(ext, 96, 160)
+    out3 = (ctypes.c_int * 3)()
+    try:
+        ext.lanes = 1
+        seen = set()
+        for mode in ('fp32', 'bf16x1', 'bf16x1_3x3'):
+            ext.precision = mode
+            want_n, want_flops = {S1: 0, S2: 0, 6: 0}, [0.0, 0.0, 0.0, 0.0]
+            for idx, (cout, cin, k, s, pad), (h, w) in convs:
+                assert _lib().frtm_backbone_conv_route(ext._handle, idx, B, h, w, out3) == 0
+                lay, _, slot = tuple(out3)
+                if lay in want_n:
+                    want_n[lay] += 1
+                seen.add(lay)
+                ho, wo = (h + 2 * pad - k) // s + 1, (w + 2 * pad - k) // s + 1
+                want_flops[slot] += 2.0 * cout * B * ho * wo * cin * k * k
+            _, n = _pass(ext, img)
+            assert n == (want_n[S1], want_n[S2], want_n[6]), (mode, n, want_n)
+            assert list(ext.last_flops_form) == want_flops, (mode, ext.last_flops_form, want_flops)
+            assert ext.last_flops == sum(want_flops) and ext.last_conv_launches == len(convs)
+        assert {0, 1, S1, S2} <= seen and (name == 'resnet18' or 6 in seen), seen          # (the query was asked about routes of every kind)
+    finally:
+        ext.precision = 'fp32'
+
+
 def test_reupload_packs_the_3x3_images_again():
     """frtm_backbone_set_conv after the flag is on packs the bf16 images from the new weights (here: the same ones, so the taps are bit-identical)."""
     ext, img, _ = _trunk('resnet18')
@@ -431,7 +488,7 @@ def test_reupload_packs_the_3x3_images_again():
         ext.precision = 'fp32'
 
 
-# (Cin, Cout, stride) -> fewest columns per launch from which backbone.hip's kBf16x1Rules3x3 routes the shape (profiles/bf16x1_trunk3x3_time.txt)
+# (Cin, Cout, stride) -> fewest columns per launch from which trunk_route.h's kTrunkRules routes the shape (profiles/bf16x1_trunk3x3_time.txt)
 DEFAULT_RULES_3X3 = {(64, 64, 1): 25680, (128, 128, 1): 6420, (256, 256, 1): 12960, (512, 512, 1): 3240, (128, 128, 2): 6420, (256, 256, 2): 12960,
                      (512, 512, 2): 3240, (64, 128, 2): 6420, (128, 256, 2): 1620, (256, 512, 2): 3240}
 

@@ -244,7 +244,7 @@ def test_ineligible_pack_is_an_argument_error():
 
 
 def routed_convs(ext, lane_frames=8, hw=405):
-    """Indices of the convs a bf16x3 trunk sends to the bf16x3 kernel at `lane_frames` frames per lane of 480x854 (backbone.hip: bf16x3_route:
+    """Indices of the convs a bf16x3 trunk sends to the bf16x3 kernel at `lane_frames` frames per lane of 480x854 (csrc/trunk_route.h: kTrunkRules:
     layer4's 512 -> 2048 conv3 with >= 3240 columns; hw = its 15x27 map)."""
     from frtm_vos_amd import _hip as H
     info = (ctypes.c_int * 6)()

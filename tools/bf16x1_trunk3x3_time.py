@@ -6,7 +6,7 @@ tests/test_bf16x1_trunk3x3_gpu.py and the dataset-level J&F on the sequences of 
 
 Operands are trunk activations of synthetic 480x854 frames (the clock drops on random data): taps of seeded passes, through the conv1 + BN + ReLU of
 a bottleneck block for ResNet-101's 3x3 convs; weights are that block's 3x3 conv (BN folded).  The arms alternate in one process.  The routing rule
-of csrc/backbone.hip (kBf16x1Rules3x3) is read off the per-shape table: a shape is routed only where the bf16 median (automatic tile form) beats the
+of csrc/trunk_route.h (kTrunkRules) is read off the per-shape table: a shape is routed only where the bf16 median (automatic tile form) beats the
 median of the fp32 form by more than the spread (max - min) of the fp32 arm's own per-round figures in this run.
     python tools/bf16x1_trunk3x3_time.py [--quick] [--sections shapes,passes,oracle,emulation,tracker,jf] [--append]"""
 import copy
@@ -82,34 +82,26 @@ def ab(fns, n, rounds):
     return [(statistics.median(v), max(v) - min(v)) for v in t]
 
 
-def ceil_div(a, b):
-    return -(-a // b)
+FORM_NAMES = {1: 'halo', 2: 'wino', 3: 'wino4', 4: 'wino6'}          # FRTM_WLAYOUT_HALO3X3, _WINO3X3, _WINO4, _WINO6
 
 
-def fp32_form(cin, cout, stride, B, ho, wo):
-    """The fp32 form csrc/backbone.hip: run_conv takes for a 3x3 pad-1 conv of the default trunk (Winograd on, F(4x4) / F(6x6) on, 256 product tiles):
-    'wino6' / 'wino4' (three launches), 'wino' (fused F(2x2,3x3)) or 'halo' (the direct kernel, the only form of a stride-2 conv)."""
-    if stride == 1 and cin >= 128 and cin % 32 == 0 and cout % 64 == 0:
-        best = None
-        for m in (6, 4):
-            th, tw, NP = ceil_div(ho, m), ceil_div(wo, m), (m + 2) ** 2
-            T = B * th * tw
-            Tp = ceil_div(T, 64) * 64
-            if ceil_div(cout, 64) * (NP * Tp // 64) < 256 or m * m * th * tw * 4 > 5 * ho * wo:
-                continue
-            if best is None or NP * Tp < best[1]:
-                best = (m, NP * Tp)
-        if best:
-            return 'wino%d' % best[0]
-    if stride == 1 and B * ceil_div(ho, 8) * ceil_div(wo, 8) * ceil_div(cout, 32) >= ops.WINO_MIN_BLOCKS:
-        return 'wino'
-    return 'halo'
+def trunk_form(ext, cin, cout, stride, B, hi, wi):
+    """The fp32 form the trunk `ext` (in fp32 mode) takes for its 3x3 pad-1 conv of this shape on B images of hi x wi, asked from its own handle
+    (frtm_backbone_conv_route): 'wino6' / 'wino4' (three launches), 'wino' (fused F(2x2,3x3)) or 'halo' (the direct kernel, the only form of a
+    stride-2 conv)."""
+    info, out3 = (ctypes.c_int * 6)(), (ctypes.c_int * 3)()
+    for idx in range(H.lib().frtm_backbone_num_convs(ext._handle)):
+        H.call_nostream('frtm_backbone_conv_info', ext._handle, idx, info)
+        if tuple(info[:4]) == (cout, cin, 3, stride):
+            H.call_nostream('frtm_backbone_conv_route', ext._handle, idx, B, hi, wi, out3)
+            return FORM_NAMES[out3[0]]
+    raise ValueError('%s has no 3x3 conv %d -> %d of stride %d' % (ext.name, cin, cout, stride))
 
 
 def shapes_section():
     g = torch.Generator().manual_seed(0)
     img8 = torch.randint(0, 256, (8, 3, 480, 854), dtype=torch.uint8, generator=g).to(DEV)
-    cases = []          # (name, x8, weights, scale, shift, stride)
+    cases = []          # (name, x8, weights, scale, shift, stride, the trunk the conv belongs to)
     for arch in ('resnet101', 'resnet18'):
         ext = ResnetFeatureExtractor(arch, seed=0).to(DEV)
         ext.lanes = 2
@@ -126,18 +118,17 @@ def shapes_section():
                     wp1, kt1, _ = ops.pack_weights(w1.to(DEV))
                     x8 = ops.conv2d(t, wp1, w1.shape[0], 1, 1, 0, ktab=kt1, scale=s1.to(DEV), shift=b1.to(DEV), relu=True)
                     w, sc, sh = folded(blk.conv2, blk.bn2)
-                    cases.append(('rn101 %d->%d s%d' % (w.shape[1], w.shape[0], stride), x8, w, sc, sh, stride))
+                    cases.append(('rn101 %d->%d s%d' % (w.shape[1], w.shape[0], stride), x8, w, sc, sh, stride, ext))
             else:
                 # the stride-1 shapes are ResNet-101's (N -> N on the stage's map): measured once, above; stride 2: block 0's conv1 on the previous tap
                 if s:
                     w, sc, sh = folded(layer[0].conv1, layer[0].bn1)
-                    cases.append(('rn18 %d->%d s2' % (w.shape[1], w.shape[0]), prev, w, sc, sh, 2))
-        del ext
+                    cases.append(('rn18 %d->%d s2' % (w.shape[1], w.shape[0]), prev, w, sc, sh, 2, ext))
     say('%-18s %2s %8s %6s %-6s %8s %6s %8s %8s %8s %9s %9s  %-46s %10s %10s %10s %10s' % (
         'shape', 'B', 'out map', 'cols', 'form', 'fp32 us', '+-', 't64 us', 't96 us', 'floor us', 'fp32/auto', 'MHz f/b', 'fp32 kernels', 'max e f32', 'max e b1',
         'rms e f32', 'rms e b1'))
     verdicts = []
-    for name, x8, w, sc, sh, stride in cases:
+    for name, x8, w, sc, sh, stride, ext in cases:
         cout, cin = w.shape[0], w.shape[1]
         wd, scd, shd = w.to(DEV), sc.to(DEV), sh.to(DEV)
         wB, _, layB = ops.pack_weights(wd, bf16x1=True, stride=stride)
@@ -147,7 +138,7 @@ def shapes_section():
             hi, wi = x.shape[2], x.shape[3]
             ho, wo = (hi - 1) // stride + 1, (wi - 1) // stride + 1
             cols = B * ho * wo
-            form = fp32_form(cin, cout, stride, B, ho, wo)
+            form = trunk_form(ext, cin, cout, stride, B, hi, wi)
             if form not in packs:
                 packs[form] = ops.pack_weights(wd, wino=form == 'wino', wino4=form == 'wino4', wino6=form == 'wino6')
             wT, kt, lay = packs[form]
@@ -190,7 +181,7 @@ def passes_section():
     g = torch.Generator().manual_seed(0)
     img8 = torch.randint(0, 256, (8, 3, 480, 854), dtype=torch.uint8, generator=g).to(DEV)
     img16 = torch.cat([img8, img8.roll(7, dims=3)])
-    say('# trunk pass (all five taps), eager, median of alternating rounds, routing as compiled (csrc/backbone.hip: kBf16x1Rules, kBf16x1Rules3x3)')
+    say('# trunk pass (all five taps), eager, median of alternating rounds, routing as compiled (csrc/trunk_route.h: kTrunkRules)')
     for arch in ('resnet101', 'resnet18'):
         ext = ResnetFeatureExtractor(arch, seed=0).to(DEV)
         for B, lanes in ((16, 2), (8, 2), (1, 1)):                 # 16 frames in 2 lanes: the tracker's trunk batches (feature_batch 16)

@@ -6,7 +6,7 @@ Writes profiles/bf16x1_trunk_time.txt.
 Operands are trunk activations of synthetic 480x854 frames (the clock drops on random data): the taps of a seeded ResNet-101 pass, through the
 conv1 + BN + ReLU of the next block of that stage for the narrow inputs; weights are that block's conv3 (BN folded); the conv1 shapes (N -> N / 4)
 run on the tap itself.  The arms alternate in
-one process; frtm_clock_probe reports the shader clock under each arm's load.  The routing rule of csrc/backbone.hip (kBf16x1Rules) is read off
+one process; frtm_clock_probe reports the shader clock under each arm's load.  The routing rule of csrc/trunk_route.h (kTrunkRules) is read off
 the per-shape table: a shape is routed only where the bf16x1 median (automatic tile form) beats the fp32 median by more than the spread (max - min)
 of the fp32 arm's own per-round figures in this run.
     python tools/bf16x1_trunk_time.py [--quick] [--no-tracker] [--no-jf]
@@ -181,7 +181,7 @@ def main():
     for v in verdicts:
         say('#   ' + v)
     # whole trunk passes
-    say('# ResNet-101 trunk pass (all five taps), eager, median of alternating rounds, routing as compiled (csrc/backbone.hip: kBf16x1Rules)')
+    say('# ResNet-101 trunk pass (all five taps), eager, median of alternating rounds, routing as compiled (csrc/trunk_route.h: kTrunkRules)')
     img16 = torch.cat([img8, img8.roll(7, dims=3)])
     for B, lanes in ((16, 2), (8, 2), (1, 1)):                 # 16 frames in 2 lanes: the tracker's trunk batches (feature_batch 16)
         ext.lanes = lanes

@@ -1,17 +1,28 @@
 """The trunk alone, exactly as bench.py drives it (RN101, 480x854, 4 frames per pass): HIP-event timing per pass and, under
 `rocprofv3 --kernel-trace --stats`, a kernel trace that contains nothing but trunk kernels -- the one-to-one cross-check of
-bench.py's roofline.per_launch numbers (sum of conv-family kernel durations / conv launches)."""
+bench.py's roofline.per_launch numbers (sum of conv-family kernel durations / conv launches).
+    python tools/trunk_bench.py [frames [lanes [graph] [queues] [sync]]] [--precision=fp32|bf16x3|bf16x1|bf16x1_3x3] [--lib=path/to/libfrtm_hip.so]
+--lib: another build of the library (an A/B of two builds: one process per build, alternating)."""
+import ctypes
 import os
 import sys
 
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from frtm_vos_amd import _hip as H  # noqa: E402
+
+OPTS = dict(a[2:].split('=', 1) for a in sys.argv[1:] if a.startswith('--'))
+sys.argv = [a for a in sys.argv if not a.startswith('--')]
+if 'lib' in OPTS:
+    H.LIB_PATH = os.path.abspath(OPTS['lib'])          # before the first call loads it
+    for name in [n for n in H.SIGNATURES if not hasattr(ctypes.CDLL(H.LIB_PATH), n)]:          # an older build: bind what it has
+        del H.SIGNATURES[name]
 from frtm_vos_amd.model.feature_extractor import ResnetFeatureExtractor  # noqa: E402
 
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 4
 LANES = int(sys.argv[2]) if len(sys.argv) > 2 else 1
-ext = ResnetFeatureExtractor('resnet101').to('cuda:0')
+ext = ResnetFeatureExtractor('resnet101', precision=OPTS.get('precision', 'fp32')).to('cuda:0')
 ext.reuse_outputs = True
 ext.lanes = LANES
 ext.use_graph = len(sys.argv) > 3 and sys.argv[3] == 'graph'
