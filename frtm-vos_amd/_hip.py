@@ -152,6 +152,10 @@ SIGNATURES = {
     'frtm_resize_frames_u8': (I, [P, ctypes.c_size_t, P, P, I, I, P, I, I, P]),
     'frtm_target_apply_grouped': (I, [P, ctypes.c_size_t, I, P, P, P, I, I, I, I, I, P, P, P]),
     'frtm_resize_labels_u8': (I, [P, ctypes.c_size_t, P, P, I, P, I, I, P]),
+    'frtm_tse_inject_indexed': (I, [P, P, P, P, I, P, I, I, I, I, I, I, P, P]),
+    'frtm_cab_gate_indexed': (I, [P, P, P, I, P, P, P, P, I, I, P, P]),
+    'frtm_cab_combine_indexed': (I, [P, P, P, P, I, I, I, I, I, I, I, P, P]),
+    'frtm_track_merge_ragged': (I, [P, I, P, I, P, P, F, P]),
 }
 
 _lib = None

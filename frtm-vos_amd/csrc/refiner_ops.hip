@@ -6,14 +6,6 @@
 #include "resample_taps.h"
 #include "../../include/frtm_hip.h"
 
-__device__ __forceinline__ float bilinear_at(const float* __restrict__ p, int h, int w, int H, int W, int y, int x) {
-  if (h == H && w == W) return p[y * w + x];
-  int y0, y1, x0, x1; float ly0, ly1, lx0, lx1;
-  bilinear_taps(y, (float)h / (float)H, h, y0, y1, ly0, ly1);
-  bilinear_taps(x, (float)w / (float)W, w, x0, x1, lx0, lx1);
-  return ly0 * (lx0 * p[y0 * w + x0] + lx1 * p[y0 * w + x1]) + ly1 * (lx0 * p[y1 * w + x0] + lx1 * p[y1 * w + x1]);
-}
-
 // out[pl] = bilinear(in[pl], (h,w) -> (H,W)) for `planes` maps.  One thread per output pixel computes the four taps once and
 // walks all planes (coalesced along x in both tensors), instead of redoing the tap arithmetic per plane.
 __global__ __launch_bounds__(256) void k_bilinear_resize(const float* __restrict__ in, int h, int w, float* __restrict__ out, int H, int W,

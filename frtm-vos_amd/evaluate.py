@@ -104,16 +104,17 @@ class Parameters:
         return mdl
 
 
-    def get_stream_pool(self, max_streams=8, grouped_apply=False, min_pairs=None):
+    def get_stream_pool(self, max_streams=8, grouped_apply=False, min_pairs=None, ragged_groups=False):
         """A StreamPool (model/stream_pool.py) over the modules get_model() builds: one augmenter, trunk and refiner for up to
-        ``max_streams`` live streams, each with target models of its own."""
+        ``max_streams`` live streams, each with target models of its own.  ``ragged_groups``: streams with different object counts share
+        one refiner pass and one merge (StreamPool's option of that name)."""
         from .model.stream_pool import StreamPool
         if torch.device(self.device).type != 'cuda':
             raise RuntimeError('get_stream_pool: device %s; the FRTM hot path runs on the GPU only (no CPU fallback)' % (self.device,))
         mdl = self.get_model()
         extra = {} if min_pairs is None else dict(min_pairs=int(min_pairs))
         return StreamPool(mdl.augmenter, mdl.feature_extractor, self.disc_params, mdl.refiner, self.device, max_streams=max_streams,
-                          grouped_apply=grouped_apply, trunk_lanes=self.trunk_lanes, **extra)
+                          grouped_apply=grouped_apply, trunk_lanes=self.trunk_lanes, ragged_groups=ragged_groups, **extra)
 
 
 def parse_args(argv=None):

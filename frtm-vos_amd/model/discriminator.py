@@ -801,14 +801,26 @@ def apply_grouped(discs, feats, pairs_per_frame, cache, cft=None, scores=None):
     """``Discriminator.apply`` for G target models in ONE launch pair (ops.target_apply_grouped): pair p is (frame p // pairs_per_frame of
     ``feats``, discs[p]).  -> (cft (G,c,h,w), scores (G,1,h,w)); both may be given (dense workspaces the caller reuses).
     ``cache``: a dict the caller keeps for this set of pairs; it holds the device pointer tables, which are rebuilt when a pointer or the
-    device changes -- a target model re-fitted, re-loaded or replaced by another one; a filter re-solve writes in place: no change."""
+    device changes -- a target model re-fitted, re-loaded or replaced by another one; a filter re-solve writes in place: no change.
+    ``pairs_per_frame`` may also be a tuple of per-frame counts, or the ops.RaggedTable of those counts (frames with different numbers of
+    pairs, pairs frame-major): the frame table is then the RaggedTable's ``frame_of`` -- the table the refiner takes as well; built from
+    a tuple it is kept as ``cache['table']``."""
     dev = feats.device
     w1T = [d._project_T() for d in discs]
     ptrs = [t.data_ptr() for t in w1T] + [d.filter.weight.data_ptr() for d in discs]
     if cache.get('ptrs') != ptrs or cache.get('dev') != dev:
-        pairs = (len(discs), pairs_per_frame, dev)
-        if cache.get('pairs') != pairs:
-            cache.update(pairs=pairs, frames=H.upload(torch.arange(len(discs), dtype=torch.int32) // pairs_per_frame, dev))
+        table = pairs_per_frame if isinstance(pairs_per_frame, ops.RaggedTable) else None
+        per_frame = table.counts if table is not None else pairs_per_frame
+        pairs = (len(discs), per_frame, dev)
+        if cache.get('pairs') != pairs or (table is not None and cache.get('table') is not table):
+            if isinstance(per_frame, tuple):
+                if table is None:
+                    table = ops.RaggedTable(per_frame, dev)
+                if table.n != len(discs):
+                    raise ValueError('apply_grouped: %d target models for %r pairs per frame' % (len(discs), per_frame))
+                cache.update(pairs=pairs, table=table, frames=table.frame_of)
+            else:
+                cache.update(pairs=pairs, frames=H.upload(torch.arange(len(discs), dtype=torch.int32) // pairs_per_frame, dev))
         cache.update(ptrs=ptrs, dev=dev, w1T=ops.pointer_table(w1T, dev), w2=ops.pointer_table([d.filter.weight.data for d in discs], dev))
     cft, scores = ops.target_apply_grouped(feats, cache['frames'], cache['w1T'], cache['w2'], discs[0].project.out_channels,
                                            cft=cft, scores=scores)

@@ -256,17 +256,25 @@ class SegNetwork(nn.Module):
         first = next(iter(self.ft_channels))
         return red, F.adaptive_avg_pool2d(red[first], (1, 1))
 
-    def forward(self, scores, features, image_size, shared=None):
+    def forward(self, scores, features, image_size, shared=None, frame_of=None):
         """scores: (F*n,1,h,w) coarse scores of n objects on each of F frames, frame-major (sample = f*n + k); features: backbone
         taps of those F frames, (F,C,H,W) each (F = 1: the n objects of one frame); returns (F*n,1,H,W) logits.  The reference
         (seg_network.py:176-189) evaluates one object of one frame per call; frames between two filter re-solves do not depend
-        on each other, so the tracker hands over a whole window of them."""
+        on each other, so the tracker hands over a whole window of them.
+        frame_of: an ops.RaggedTable when the frames carry DIFFERENT numbers of objects (scores (table.n,1,h,w), still frame-major): the
+        three places that find a sample's frame -- the TSE base map, the deepest CAB's pooled vector in its gate and its combine -- read
+        the table (csrc/ragged_group.hip); everything else is per sample.  Such a call is never replayed from a graph."""
+        if frame_of is not None:
+            frames = features[next(iter(self.ft_channels))].shape[0]
+            if scores.shape[0] != frame_of.n or frames != frame_of.F:
+                raise ValueError('scores (%d samples) and taps (%d frames) do not match the table: %d frames of %r objects'
+                                 % (scores.shape[0], frames, frame_of.F, frame_of.counts))
         if scores.is_cuda and shared is None:
             if self.training or torch.is_grad_enabled():
                 raise RuntimeError('SegNetwork.forward on the GPU is the inference path (HIP kernels, no autograd): call it in eval() mode '
                                    'under torch.no_grad(); for training / gradients call forward_torch(...) explicitly '
                                    '(the PyTorch definition of the same network) or forward_train(...) (HIP kernels with autograd)')
-            if self.use_graphs:
+            if self.use_graphs and frame_of is None:
                 return self._forward_graphed(scores, features, image_size)
             # launched kernel by kernel: the deep pyramid levels still run on the shared side stream next to the 120x214 level (round 6:
             # what a graph replay gains over serial launches is this overlap, not the launch count -- the host enqueues ahead of the GPU)
@@ -274,13 +282,17 @@ class SegNetwork(nn.Module):
             #  streaming 317.7 -> 312 frames/s; windows of 5-8 frames gain 5-6 %: profiles/r06_refiner_window_ab.txt)
             par = (self.parallel_levels and self.parallel_eager and next(iter(features.values())).shape[0] >= 2
                    and not torch.cuda.is_current_stream_capturing())
-            return self._forward_hip(scores, features, image_size, self._side_streams() if par else None)
-        return self.forward_torch(scores, features, image_size, shared)
+            return self._forward_hip(scores, features, image_size, self._side_streams() if par else None, frame_of)
+        return self.forward_torch(scores, features, image_size, shared, frame_of)
 
-    def forward_torch(self, scores, features, image_size, shared=None):
+    def forward_torch(self, scores, features, image_size, shared=None, frame_of=None):
         red, pool = shared if shared is not None else self.precompute(features)
         group = scores.shape[0] // pool.shape[0]
-        if pool.shape[0] > 1:                         # several frames: every frame's maps serve its `group` objects
+        if frame_of is not None:                      # frames with different object counts: every sample takes its frame's maps
+            idx = frame_of.frame_of.to(scores.device)
+            red = {L: t.index_select(0, idx) for L, t in red.items()}
+            pool = pool.index_select(0, idx)
+        elif pool.shape[0] > 1:                       # several frames: every frame's maps serve its `group` objects
             red = {L: t.repeat_interleave(group, 0) for L, t in red.items()}
             pool = pool.repeat_interleave(group, 0)
         x = None
@@ -428,20 +440,20 @@ class SegNetwork(nn.Module):
         a = self._conv(x, r['c1'])
         return self._conv(self._conv(a, r['b0']), r['b1'], residual=a)
 
-    def _branch(self, L, p, ft, scores, deepest):
+    def _branch(self, L, p, ft, scores, deepest, table=None):
         """Everything of one pyramid level that does not need the deeper level's output: TSE (reduce shared by all objects of a
         frame, score channel injected into transform[0]) and RRB1 (reference seg_network.py:168-171) + the CAB's shallow pool.
-        ft: (F,fc,H,W) taps of F frames; scores: (F*n,1,h,w), frame-major."""
+        ft: (F,fc,H,W) taps of F frames; scores: (F*n,1,h,w), frame-major; table: the frames' object counts when they differ."""
         group = scores.shape[0] // ft.shape[0]
         h = self._conv(self._conv(ft, p['r0']), p['r2'])                       # TSE.reduce, shared by the objects of a frame
         pool0 = ops.plane_mean(h) if deepest else None                         # (F,oc): deeper input of the deepest CAB
         base = self._conv(h, p['base'])                                        # object-independent part of transform[0]
-        t0 = ops.tse_inject(base, p['b0'], p['ws'], scores, group)
+        t0 = ops.tse_inject(base, p['b0'], p['ws'], scores, group) if table is None else ops.tse_inject_indexed(base, p['b0'], p['ws'], scores, table)
         t = self._conv(self._conv(t0, p['t2']), p['t4'])
         r = self._rrb_hip(t, p['rrb1'])
         return r, ops.plane_mean(r), pool0, (h, base, t0, t)
 
-    def _forward_hip(self, scores, features, image_size, side_streams=None):
+    def _forward_hip(self, scores, features, image_size, side_streams=None, table=None):
         """side_streams: optional list of torch streams, one entry per pyramid level but the last (entries may repeat).  The
         per-level branches do not depend on each other -- only the CAB / RRB2 tail chains the levels, deep to shallow -- so
         they may run concurrently and the small deep-level kernels (15x27, 30x54: a few workgroups each) hide under the
@@ -452,7 +464,7 @@ class SegNetwork(nn.Module):
         scores = scores.float().contiguous()
         n = scores.shape[0]                                     # samples = frames x objects, frame-major
         frames = features[next(iter(self.ft_channels))].shape[0]
-        if n % frames != 0:
+        if table is None and n % frames != 0:
             raise ValueError('scores (%d samples) must hold the same number of objects for each of the %d frames' % (n, frames))
         group = n // frames
         levels = list(self.ft_channels)
@@ -475,10 +487,10 @@ class SegNetwork(nn.Module):
             ft = features[L].contiguous()
             st = side_streams[i] if (side_streams and i < len(side_streams)) else None
             if st is None:
-                br[L] = self._branch(L, P[L], ft, scores, i == 0)
+                br[L] = self._branch(L, P[L], ft, scores, i == 0, table)
             else:
                 with torch.cuda.stream(st):
-                    br[L] = self._branch(L, P[L], ft, scores, i == 0)
+                    br[L] = self._branch(L, P[L], ft, scores, i == 0, table)
         x, pool0 = None, br[levels[0]][2]
         for i, L in enumerate(levels):
             p = P[L]
@@ -487,7 +499,7 @@ class SegNetwork(nn.Module):
                 order(cur, st)
             r, sp, _, tmp = br[L]
             keep.append(tmp)
-            out, gate, dp = cab_level(r, sp, x, pool0, (p['cab_w1'], p['cab_b1'], p['cab_w2'], p['cab_b2']), group)
+            out, gate, dp = cab_level(r, sp, x, pool0, (p['cab_w1'], p['cab_b1'], p['cab_w2'], p['cab_b2']), group, table)
             keep.append((x, gate, out, dp))
             x = self._rrb_hip(out, p['rrb2'])
         pj = P['project']
@@ -499,14 +511,18 @@ class SegNetwork(nn.Module):
         return project_head(y, pj['w2'], pj['b2'], image_size, pj['kind'] == 'bicubic', self.fuse_tail, self.mix_taps and y.shape[1] > 9, pj['eye9'])
 
 
-def cab_level(r, sp, x, pool0, weights, group):
+def cab_level(r, sp, x, pool0, weights, group, table=None):
     """The CAB of one pyramid level on the HIP kernels, for the inference and the training path: r (n,oc,H,W) the level's RRB1 output, sp
     its pooled vector, x the deeper level's output (None at the deepest level, whose deeper input is pool0 (n / group,oc), the pooled
     TSE.reduce map that the ``group`` objects of a frame share; group 0: one row per sample), weights = (w1t, b1, w2t, b2) of
-    ops.cab_gate.  Returns (out, gate, dp): the combined map, the gate before its sigmoid and the deeper pooled vector."""
+    ops.cab_gate.  ``table``: an ops.RaggedTable when the frames carry different numbers of objects; sample s then takes row
+    table.frame_of[s] of pool0.  Returns (out, gate, dp): the combined map, the gate before its sigmoid and the deeper pooled vector."""
     deepest = x is None
     dp = pool0 if deepest else ops.plane_mean(x)
     w1t, b1, w2t, b2 = weights
+    if deepest and table is not None:
+        gate = ops.cab_gate_indexed(sp, dp, w1t, b1, w2t, b2, table)
+        return ops.cab_combine_indexed(r, gate, pool0, table), gate, dp
     gate = ops.cab_gate(sp, dp, w1t, b1, w2t, b2, group if deepest else 0)
     return ops.cab_combine(r, gate, pool0 if deepest else x, group if deepest else 0), gate, dp
 

@@ -6,7 +6,8 @@ batch-1 trunk: every stream delivers one frame per tick, so the frames of all st
 number of objects share one refiner pass and one merge (and, with ``grouped_apply``, one grouped target-model launch,
 ops.target_apply_grouped).  Each stream keeps its own target models and memory: per stream the arithmetic is that of ``track()``.  The
 reference has no such API.  A group runs the step that ``track()`` and ``track_window()`` run: ``fused_step`` of
-model/tracker.py, with one list of target models per stream.
+model/tracker.py, with one list of target models per stream.  With ``ragged_groups`` the streams of a frame size share that pass whatever
+their object counts (plan_tick_ragged; the indexed kernels of csrc/ragged_group.hip).
 
     pool = Parameters(weights).get_stream_pool(max_streams=8)
     sid = pool.open()
@@ -19,6 +20,7 @@ from collections import namedtuple
 import torch
 
 from .. import _hip as H
+from .. import ops
 from .tracker import FrameTaps, Tracker, fused_step, persistent_taps
 
 TickBatch = namedtuple('TickBatch', 'size order groups fallbacks')
@@ -58,6 +60,28 @@ def plan_tick(entries):
     return TickPlan(batches, sorted(skipped))
 
 
+def plan_tick_ragged(entries):
+    """plan_tick for a pool with ``ragged_groups``: the same batches, order, fallbacks and skipped streams, but ONE group per frame size,
+    (start, g, counts): ALL eligible streams of the size, order[start:start + g], take the fused step together whatever their object
+    counts -- counts[i] active objects on stream i of the group, ascending, since the order is by count and then by sid.  A stream with
+    more than 15 active objects (the merge kernel's bound, ops.MAX_MERGE_OBJECTS) is a fallback.  Pure, and independent of the order of
+    ``entries``, like plan_tick."""
+    by_size, skipped = {}, []
+    for sid, size, n, eligible in entries:
+        if n <= 0:
+            skipped.append(sid)
+            continue
+        eligible = bool(eligible) and int(n) <= ops.MAX_MERGE_OBJECTS
+        by_size.setdefault(tuple(size), []).append((not eligible, int(n) if eligible else 0, sid))
+    batches = []
+    for size in sorted(by_size):
+        rows = sorted(by_size[size])                       # eligible streams first, by object count; then the fallbacks; by sid within
+        g = sum(1 for r in rows if not r[0])
+        groups = [(0, g, tuple(r[1] for r in rows[:g]))] if g else []
+        batches.append(TickBatch(size, [sid for _, _, sid in rows], groups, list(range(g, len(rows)))))
+    return TickPlan(batches, sorted(skipped))
+
+
 class _Stream:
     def __init__(self, tracker):
         self.tracker = tracker
@@ -67,7 +91,7 @@ class _Stream:
 class StreamPool:
 
     def __init__(self, augmenter, feature_extractor, disc_params, refiner, device, max_streams=8, grouped_apply=False, min_pairs=2,
-                 trunk_lanes=2):
+                 trunk_lanes=2, ragged_groups=False):
         """One augmenter, one trunk and one refiner for up to ``max_streams`` per-stream Tracker states built over those same modules.
         grouped_apply  True: the groups' target models score through ONE ops.target_apply_grouped launch pair; False: per pair
                        ``Discriminator.apply(ft, interleave=...)`` (three small launches each) -- the A/B of tools/stream_pool_time.py.
@@ -77,7 +101,14 @@ class StreamPool:
                        arm's own max - min over its 24 ticks (0.21 / 0.77 / 1.06 ms).
         min_pairs      pair count (streams x objects of a group) from which the grouped launch is used when grouped_apply is on.  The
                        measurement names no count (see above), so the starting value 2 stands: one pair gains nothing from grouping
-                       (measured at 2 pairs: +0.02 ms)."""
+                       (measured at 2 pairs: +0.02 ms).
+        ragged_groups  True: all eligible streams of one frame size take the fused step together whatever their object counts
+                       (plan_tick_ragged): one refiner pass, one merge and, with grouped_apply, one grouped scoring launch per frame size
+                       and tick, on the indexed kernels of csrc/ragged_group.hip; a group whose counts are all equal runs exactly as
+                       without the option.  False (default): streams share a pass only when their object counts are equal (plan_tick) -- same
+                       launches, same bits as before the option existed.  Measured at 480x854 / RN101 (profiles/stream_pool_ragged_time.txt):
+                       8 streams with 1, 1, 2, 2, 3, 3, 4 and 5 objects 14.59 -> 12.68 ms per tick against a max - min of 0.33 ms, 4 streams
+                       with 1 .. 4 objects 8.87 -> 7.16 ms, nothing on equal counts; one measurement introduces the option, the default waits."""
         if torch.device(device).type != 'cuda':
             raise RuntimeError('StreamPool: device %s; the FRTM hot path runs on the GPU only (no CPU fallback)' % (device,))
         if int(max_streams) < 1:
@@ -88,12 +119,15 @@ class StreamPool:
         self.grouped_apply = bool(grouped_apply)
         self.min_pairs = int(min_pairs)
         self.trunk_lanes = int(trunk_lanes)
+        self.ragged_groups = bool(ragged_groups)
         self._streams = {}
         self._next_sid = 0
         self._disc_pool = []            # released target models, shared by all streams (Tracker.release_targets)
-        self._bufs = {}                 # (kind, g, n, size) -> preallocated device tensor
-        self._tables = {}               # (g, n, size) -> apply_grouped's table cache of the group that last ran under this key
+        self._bufs = {}                 # (kind, g, n, size) or (kind, counts, size) -> preallocated device tensor
+        self._tables = {}               # (g, n, size) or (counts, size) -> apply_grouped's table cache of the group that last ran under this key
+        self._ragged = {}               # (counts, size) -> ops.RaggedTable: one table for the scoring, the refiner and the merge
         self.grouped_launches = 0       # ops.target_apply_grouped calls so far (diagnostics)
+        self.refiner_passes = 0         # refiner calls made by groups so far (diagnostics)
 
     # ---- streams ------------------------------------------------------------------------------------------------------------
     def open(self):
@@ -152,7 +186,7 @@ class StreamPool:
                 tr._check_first_frame_fits()            # as track(): no frame is scored with a half-fitted model
             active = active_of[sid] = tr.active_targets()
             entries.append((sid, tuple(image.shape[-2:]), len(active), self._eligible(tr, active)))
-        plan = plan_tick(entries)
+        plan = plan_tick_ragged(entries) if self.ragged_groups else plan_tick(entries)
         out = {}
         ext = self.feature_extractor
         for tb in plan.batches:
@@ -181,7 +215,12 @@ class StreamPool:
 
     def _run_group(self, tb, start, g, n, taps, active_of, out):
         """The fused step (model/tracker.py: fused_step) for g streams of n objects at once, one frame each, on the pool's buffers:
-        pair p = i * n + k is (stream i of the group, its object k)."""
+        pair p = i * n + k is (stream i of the group, its object k).  n a tuple (plan_tick_ragged): stream i carries n[i] objects."""
+        self.refiner_passes += 1
+        if isinstance(n, tuple):
+            if len(set(n)) > 1:
+                return self._run_ragged_group(tb, start, n, taps, active_of, out)
+            n = n[0]                                    # equal counts: exactly the uniform group
         key = (g, n, tb.size)
         sids = tb.order[start:start + g]
         first = active_of[sids[0]][0]
@@ -201,3 +240,31 @@ class StreamPool:
             st.tracker.current_masks = masks[i]
             st.pool_masks = True
             out[sid] = masks[i]
+
+    def _run_ragged_group(self, tb, start, counts, taps, active_of, out):
+        """_run_group for streams with different object counts: pairs stream-major, stream i's masks the planes table.planes(i) of ONE
+        packed merge buffer.  Buffers and tables are kept per (counts, size): steady ticks allocate nothing."""
+        key = (counts, tb.size)
+        g = len(counts)
+        sids = tb.order[start:start + g]
+        first = active_of[sids[0]][0]
+        feats = {L: t[start:start + g] for L, t in taps.items()}
+        h_, w_ = feats[first.disc_layer].shape[-2:]
+        table = self._ragged.get(key)
+        if table is None:
+            table = self._ragged[key] = ops.RaggedTable(counts, self.device)
+        P = table.n
+        grouped = None
+        if self.grouped_apply and P >= self.min_pairs:
+            grouped = (self._tables.setdefault(key, {}), self._buf('cft', key, (P, first.discriminator.project.out_channels, h_, w_)))
+            self.grouped_launches += 1
+        update = bool(self.disc_params.update_filters)
+        masks, _ = fused_step(self.refiner, [active_of[sid] for sid in sids], feats, tb.size, update,
+                              scores=self._buf('scores', key, (P, 1, h_, w_)), masks=self._buf('masks', key, (P + g,) + tb.size),
+                              counts=self._buf('counts', key, (P + g,), torch.int32) if update else None, grouped=grouped, table=table)
+        for i, sid in enumerate(sids):
+            st = self._streams[sid]
+            a, b = table.planes(i)
+            st.tracker.current_masks = masks[a:b]
+            st.pool_masks = True
+            out[sid] = masks[a:b]

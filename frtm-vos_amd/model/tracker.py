@@ -162,16 +162,24 @@ def update_targets(active, cfts, masks, counts, update_filters, windowed):
 
 
 def fused_step(refiner, frame_targets, feats, size, update_filters, windowed=False, scores=None, masks=None, counts=None,
-               lut=None, single=False, grouped=None):
+               lut=None, single=False, grouped=None, table=None):
     """The tracking step of F frames of n objects each when every mask plane comes from the refiner (Tracker.fused_tail): scores into
     one frame-major batch, refiner, then sigmoid + merge + pixel counts + label decoding as ONE kernel (ops.track_merge), then
     update_targets.  ``frame_targets[f]``: the n TargetObjects of frame f; consecutive frames that share a list are scored as one
     window.  track(): F = 1; track_window(): W frames, one list; a StreamPool group: one list per stream.  ``scores`` / ``masks`` /
     ``counts``: the caller's buffers (else allocated); ``lut``: labels are decoded through it; ``grouped`` = (table cache, cft workspace):
-    one grouped launch scores all pairs (apply_grouped; every frame has its own list).  -> (masks (F,n+1,H,W), labels (F,1,H,W) or None)."""
+    one grouped launch scores all pairs (apply_grouped; every frame has its own list).  -> (masks (F,n+1,H,W), labels (F,1,H,W) or None).
+    Frames whose lists differ in length (a StreamPool group of streams with different object counts) take the same step on the indexed
+    launches: one ops.RaggedTable (``table``: the caller's, else built here) serves the grouped scoring, the refiner and
+    ops.track_merge_ragged; ``scores`` is then (N,1,h,w) with N the sum of the counts and ``masks`` (N + F,H,W) / ``counts`` (N + F) are
+    packed, frame f's n_f + 1 planes at table.planes(f).  No labels there: -> (masks packed, None)."""
     F_, n = len(frame_targets), len(frame_targets[0])
     ft = feats[frame_targets[0][0].disc_layer]
     dev = ft.device
+    if F_ > 1 and any(len(ts) != n for ts in frame_targets):
+        if lut is not None:
+            raise ValueError('fused_step: no label decoding for frames with different object counts')
+        return _fused_step_ragged(refiner, frame_targets, feats, size, update_filters, scores, masks, counts, grouped, table), None
     if scores is None:
         scores = torch.empty(F_ * n, 1, *ft.shape[-2:], device=dev)
     cuts = [f for f in range(F_) if f == 0 or frame_targets[f] is not frame_targets[f - 1]] + [F_]
@@ -194,6 +202,36 @@ def fused_step(refiner, frame_targets, feats, size, update_filters, windowed=Fal
     for (f0, f1), cft in zip(runs, cfts):
         update_targets(frame_targets[f0], cft, part(masks, f0, f1), None if counts is None else part(counts, f0, f1), update_filters, windowed)
     return masks, labels
+
+
+def _fused_step_ragged(refiner, frame_targets, feats, size, update_filters, scores, masks, counts, grouped, table):
+    """fused_step for frames whose lists differ in length (see there): one refiner pass and one merge for all of them.  -> masks packed."""
+    ft = feats[frame_targets[0][0].disc_layer]
+    dev = ft.device
+    cnts = tuple(len(ts) for ts in frame_targets)
+    if table is None:
+        table = ops.RaggedTable(cnts, dev)
+    elif table.counts != cnts:
+        raise ValueError('fused_step: the table holds %r objects per frame, the frames %r' % (table.counts, cnts))
+    F_, N = table.F, table.n
+    if scores is None:
+        scores = torch.empty(N, 1, *ft.shape[-2:], device=dev)
+    if grouped is not None:
+        apply_grouped([t.discriminator for ts in frame_targets for t in ts], ft, table, grouped[0], cft=grouped[1], scores=scores)
+        cfts = [None] * F_
+    else:                                                                                # each frame's targets into its slice of the batch
+        cfts = [[t.discriminator.apply_window(feats[t.disc_layer][f:f + 1], interleave=(scores[table.starts[f]:table.starts[f + 1]], k, len(ts)))[0]
+                 for k, t in enumerate(ts)] for f, ts in enumerate(frame_targets)]
+    logits = refiner(scores, feats, size, frame_of=table)                                # (N,1,H,W), frame-major
+    if masks is None:
+        masks = torch.empty(N + F_, *size, device=dev)
+    if counts is None and update_filters:
+        counts = torch.empty(N + F_, dtype=torch.int32, device=dev)
+    ops.track_merge_ragged(logits, table, masks, counts)
+    for f, ts in enumerate(frame_targets):
+        a, b = table.planes(f)
+        update_targets(ts, cfts[f], masks[a:b].unsqueeze(0), None if counts is None else counts[a:b].unsqueeze(0), update_filters, False)
+    return masks
 
 
 class FrameTaps(dict):

@@ -350,6 +350,98 @@ def cab_combine(shallow, gate, deeper, deeper_group=0):
     return out
 
 
+# ----------------------------------------------------------------------------------------------------------------------
+# Frames with different object counts (csrc/ragged_group.hip): the indexed twins of tse_inject / cab_gate / cab_combine / track_merge.
+# They take the table object, whose host-side counts every shape is checked against before anything touches a device.
+# ----------------------------------------------------------------------------------------------------------------------
+MAX_MERGE_OBJECTS = 15       # frtm_track_merge and frtm_track_merge_ragged: at most 15 objects per frame
+
+
+class RaggedTable:
+    """The sample-to-frame table of F frames that carry counts[f] objects each, samples frame-major: ``counts`` (host tuple), ``n`` = their
+    sum, ``F``, ``frame_of`` (device int32 (n): the frame of every sample; also the frame_of_pair table of target_apply_grouped) and
+    ``first`` (device int32 (F + 1): exclusive prefix sums; frame f owns samples first[f] .. first[f+1] - 1 and the mask planes
+    first[f] + f .. first[f+1] + f of a packed merge buffer).  Every count is 1 .. 15 (the merge kernel's bound)."""
+
+    def __init__(self, counts, device):
+        counts = tuple(int(c) for c in counts)
+        if not counts or any(c < 1 or c > MAX_MERGE_OBJECTS for c in counts):
+            raise ValueError('RaggedTable: needs at least one frame and 1 .. %d objects on each, got %r' % (MAX_MERGE_OBJECTS, counts))
+        self.counts, self.F, self.n = counts, len(counts), sum(counts)
+        starts = [0]
+        for c in counts:
+            starts.append(starts[-1] + c)
+        self.starts = tuple(starts)                                   # `first` on the host
+        self.frame_of = H.upload(torch.tensor([f for f, c in enumerate(counts) for _ in range(c)], dtype=torch.int32), device)
+        self.first = H.upload(torch.tensor(starts, dtype=torch.int32), device)
+
+    def planes(self, f):
+        """(start, stop) of frame f's n_f + 1 planes in a packed merge buffer."""
+        return self.starts[f] + f, self.starts[f + 1] + f + 1
+
+
+def tse_inject_indexed(base, bias, ws, scores, table):
+    """tse_inject for frames with different object counts: relu(base[table.frame_of[s]] + bias + conv3x3(bilinear(scores[s]), ws)); base
+    (table.F,C,H,W), scores (table.n,1,h,w) frame-major -> (table.n,C,H,W)."""
+    bs, ss = base.shape, scores.shape
+    if not (len(bs) == 4 == len(ss) and ss[1] == 1 and ss[0] == table.n and bs[0] == table.F and bias.numel() == bs[1] and ws.numel() == 9 * bs[1]
+            and base.dtype is bias.dtype is ws.dtype is scores.dtype is _F32):
+        _refuse('tse_inject_indexed', 'expected base (F,C,H,W), bias (C), ws (C,9) and scores (n,1,h,w) with F = %d frames of %r objects, '
+                'n = %d' % (table.F, table.counts, table.n), base=base, bias=bias, ws=ws, scores=scores)
+    n, c = ss[0], bs[1]
+    out = torch.empty(n, c, bs[2], bs[3], device=scores.device)
+    H.call('frtm_tse_inject_indexed', H.ptr(base), H.ptr(bias), H.ptr(ws), H.ptr(scores), n, H.ptr(table.frame_of), table.F, c, ss[2], ss[3],
+           bs[2], bs[3], H.ptr(out))
+    return out
+
+
+def cab_gate_indexed(sp, dp, w1t, b1, w2t, b2, table):
+    """cab_gate with the deeper pooled row of sample s = dp[table.frame_of[s]]: sp (table.n,oc), dp (table.F,oc)."""
+    ss, ds = sp.shape, dp.shape
+    if not (len(ss) == 2 == len(ds) and ss[0] == table.n and ds[0] == table.F and ds[1] == ss[1] and ss[1] % 4 == 0
+            and w1t.shape == (2 * ss[1], ss[1]) and w2t.numel() == ss[1] * ss[1] and b1.numel() == ss[1] == b2.numel()
+            and sp.dtype is dp.dtype is w1t.dtype is b1.dtype is w2t.dtype is b2.dtype is _F32):
+        _refuse('cab_gate_indexed', 'expected sp (n,oc), dp (F,oc) with F = %d frames of %r objects, n = %d, oc a multiple of 4, w1t (2oc,oc) and '
+                'w2t (oc,oc) as [in][out], b1 and b2 (oc)' % (table.F, table.counts, table.n), sp=sp, dp=dp, w1t=w1t, b1=b1, w2t=w2t, b2=b2)
+    n, oc = ss
+    gate = torch.empty(n, oc, device=sp.device)
+    H.call('frtm_cab_gate_indexed', H.ptr(sp), H.ptr(dp), H.ptr(table.frame_of), table.F, H.ptr(w1t), H.ptr(b1), H.ptr(w2t), H.ptr(b2), n, oc,
+           H.ptr(gate))
+    return gate
+
+
+def cab_combine_indexed(shallow, gate, deeper, table):
+    """cab_combine with the deeper entry of sample s = deeper[table.frame_of[s]]: shallow (table.n,C,H,W), gate (table.n,C), deeper
+    (table.F,C,hd,wd) or a pooled (table.F,C) vector (hd = wd = 1)."""
+    ss, ds = shallow.shape, deeper.shape
+    if not (len(ss) == 4 and gate.shape == ss[:2] and len(ds) in (2, 4) and ss[0] == table.n and ds[0] == table.F and ds[1] == ss[1]
+            and shallow.dtype is gate.dtype is deeper.dtype is _F32):
+        _refuse('cab_combine_indexed', 'expected shallow (n,C,H,W), gate (n,C) and deeper (F,C,hd,wd) or (F,C) with F = %d frames of %r objects, '
+                'n = %d' % (table.F, table.counts, table.n), shallow=shallow, gate=gate, deeper=deeper)
+    hd, wd = (ds[2], ds[3]) if len(ds) == 4 else (1, 1)
+    out = torch.empty_like(shallow)
+    H.call('frtm_cab_combine_indexed', H.ptr(shallow), H.ptr(gate), H.ptr(deeper), H.ptr(table.frame_of), table.F, ss[0], ss[1], hd, wd,
+           ss[2], ss[3], H.ptr(out))
+    return out
+
+
+def track_merge_ragged(logits, table, masks, counts=None, thr=0.5):
+    """track_merge for frames with different object counts (frtm_track_merge_ragged), no label decoding: refiner logits (table.n,1,H,W),
+    frame-major -> sigmoid -> merge per frame -> ``masks`` (table.n + table.F, H, W): frame f's n_f + 1 planes are masks[table.planes(f)];
+    optional ``counts`` (table.n + table.F) int32 = pixels above ``thr`` per plane, packed the same way."""
+    ls, ms = logits.shape, masks.shape
+    planes = table.n + table.F
+    if counts is not None and (not isinstance(counts, torch.Tensor) or counts.dtype is not torch.int32):
+        raise TypeError('track_merge_ragged: counts must be an int32 tensor, got %s' % (counts.dtype if isinstance(counts, torch.Tensor) else type(counts).__name__))
+    if not (len(ls) == 4 and ls[1] == 1 and ls[0] == table.n and len(ms) == 3 and ms[0] == planes and ms[1:] == ls[2:]
+            and (counts is None or counts.numel() == planes) and logits.dtype is masks.dtype is _F32):
+        _refuse('track_merge_ragged', 'expected logits (n,1,H,W) and masks (n + F,H,W) with F = %d frames of %r objects, n = %d, and %d counts'
+                % (table.F, table.counts, table.n, planes), logits=logits, masks=masks)
+    H.call('frtm_track_merge_ragged', H.ptr(logits), table.F, H.ptr(table.first), ls[2] * ls[3], H.ptr(masks),
+           None if counts is None else H.ptr(counts), float(thr))
+    return masks
+
+
 def tap_mix(y, w2):
     """conv2's channel sum taken before the resampling: y (n,C,h,w), w2 (1,C,3,3) -> the nine tap maps (n,9,h,w)."""
     s = y.shape

@@ -512,6 +512,27 @@ int frtm_cab_combine(const float* shallow, const float* gate, const float* deepe
  * W1 (2oc,oc) and W2 (oc,oc): the two 1x1 conv weights transposed to [in][out]. */
 int frtm_cab_gate(const float* sp, const float* dp, int dp_group, const float* W1, const float* b1, const float* W2, const float* b2,
                   int n, int oc, float* gate, frtm_stream_t stream);
+/* The indexed twins (csrc/ragged_group.hip) for frames that carry different numbers of objects: the frame of sample s comes from a
+ * device int32 table instead of s / group -- the frame_of_pair table of frtm_target_apply_grouped, so one table serves the scoring
+ * and the refiner.  Per sample the arithmetic is that of the kernel named: with the table s / group the outputs are bit-identical, and
+ * a sample's output does not depend on the rest of the launch.  A sample whose entry lies outside [0, F) (rows, entries) is skipped
+ * and its output left untouched; nothing is read or written out of bounds whatever the table holds.  Size and grid limits as the twins.
+ *   frtm_tse_inject_indexed    out[s] = relu(base[frame_of[s]] + bias + conv3x3(bilinear(scores[s]), ws)); base (F,C,H,W), frame_of int32[n]
+ *   frtm_cab_gate_indexed      frtm_cab_gate with the deeper pooled row dp[row_of[s]]; dp (rows,oc), row_of int32[n]
+ *   frtm_cab_combine_indexed   frtm_cab_combine with the deeper entry deeper[entry_of[s]]; deeper (entries,C,hd,wd), any hd, wd */
+int frtm_tse_inject_indexed(const float* base, const float* bias, const float* ws, const float* scores, int n, const int* frame_of, int F,
+                            int C, int h, int w, int H, int W, float* out, frtm_stream_t stream);
+int frtm_cab_gate_indexed(const float* sp, const float* dp, const int* row_of, int rows, const float* W1, const float* b1, const float* W2,
+                          const float* b2, int n, int oc, float* gate, frtm_stream_t stream);
+int frtm_cab_combine_indexed(const float* shallow, const float* gate, const float* deeper, const int* entry_of, int entries, int n, int C,
+                             int hd, int wd, int H, int W, float* out, frtm_stream_t stream);
+/* frtm_track_merge for frames with different object counts, without the label decoding.  first: device int32[frames + 1], the exclusive
+ * prefix sums of the per-frame counts n_f (first[0] = 0).  Frame f reads the logit planes first[f] .. first[f+1] - 1 of logits
+ * (first[frames], HW) and writes its n_f + 1 mask planes, packed, from plane first[f] + f of masks (first[frames] + frames, HW) on;
+ * counts (first[frames] + frames) int32, packed the same way, or NULL.  1 <= n_f <= 15; a frame whose entries break that, are negative
+ * or pass first[frames] is skipped, its masks and counts left untouched.  On equal counts the result is frtm_track_merge's, bit for bit. */
+int frtm_track_merge_ragged(const float* logits, int frames, const int* first, int HW, float* masks, int* counts, float thr,
+                            frtm_stream_t stream);
 /* PyrUpBicubic2d: 2x polyphase bicubic with replicate border (seg_network.py:75-126); out (planes,2h,2w) */
 int frtm_pyrup2x(const float* in, int planes, int h, int w, float* out, frtm_stream_t stream);
 /* Whether the fused tail takes a (h,w) -> (Ho,Wo) resize (1) or its LDS patch is too small for the ratio (0).  h, w: the size of the map
