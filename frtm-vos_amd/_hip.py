@@ -156,6 +156,8 @@ SIGNATURES = {
     'frtm_cab_gate_indexed': (I, [P, P, P, I, P, P, P, P, I, I, P, P]),
     'frtm_cab_combine_indexed': (I, [P, P, P, P, I, I, I, I, I, I, I, P, P]),
     'frtm_track_merge_ragged': (I, [P, I, P, I, P, P, F, P]),
+    'frtm_masks_to_native': (I, [P, ctypes.c_size_t, I, I, P, P, I, P, ctypes.c_size_t, P, ctypes.c_size_t, P, ctypes.c_size_t, P]),
+    'frtm_resize_label_map_u8': (I, [P, ctypes.c_size_t, P, P, I, P, I, I, P]),
 }
 
 _lib = None

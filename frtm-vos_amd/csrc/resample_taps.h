@@ -6,7 +6,9 @@
 // ATen bilinear source taps (upsample_bilinear2d, align_corners=False): src = max(scale * (d + .5) - .5, 0), i0 = (int)src,
 // i1 = i0 + (i0 < n_in - 1), l1 = src - i0, l0 = 1 - l1.
 __device__ __forceinline__ void bilinear_taps(int d, float scale, int n_in, int& i0, int& i1, float& l0, float& l1) {
-  float src = __fsub_rn(__fmul_rn(scale, (float)d + 0.5f), 0.5f);   // no fma contraction: same rounding as ATen's scalar code
+  // (HIP's __fmul_rn / __fsub_rn are the plain operators: hipcc contracts the two into ONE fma, as it does in ATen's own device kernel,
+  // so src is rounded once; tests/_native_refs.py: taps restates it that way and is held to torch's bilinear on the device)
+  float src = __fsub_rn(__fmul_rn(scale, (float)d + 0.5f), 0.5f);
   src = src < 0.f ? 0.f : src;
   i0 = (int)src;
   i1 = i0 + (i0 < n_in - 1 ? 1 : 0);

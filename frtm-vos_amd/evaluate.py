@@ -22,8 +22,11 @@ class Parameters:
 
     def __init__(self, weights=None, fast=False, device='cuda:0', feature_extractor=None, backbone_weights=None, feature_batch=16, trunk_lanes=2,
                  ytvos_fork_solver=False, refiner_graphs=None, aug_fill='telea', upsampler='compat', trunk_precision='fp32',
-                 refiner_precision='fp32'):
+                 refiner_precision='fp32', working_size=None):
         self.device = device
+        # (h, w): frames of any other size are resized to it on the device and tracked there; label maps and masks come back at the frames'
+        # native size (Tracker(working_size=...)).  None: frames are tracked at the size they arrive in
+        self.working_size = None if working_size is None else (int(working_size[0]), int(working_size[1]))
         if trunk_precision not in ('fp32', 'bf16x3', 'bf16x1', 'bf16x1_3x3'):
             raise ValueError("trunk_precision must be 'fp32', 'bf16x3', 'bf16x1' or 'bf16x1_3x3', got %r" % (trunk_precision,))
         self.trunk_precision = trunk_precision    # 'fp32', 'bf16x3', 'bf16x1': the trunk's routed stride-1 1x1 convs on bf16 pieces; 'bf16x1_3x3': its routed 3x3 convs too (ResnetFeatureExtractor.precision)
@@ -96,6 +99,8 @@ class Parameters:
         refiner = self.make_refiner(chans)
         refiner.precision = self.refiner_precision                 # (after make_refiner: a refiner_factory stand-in gets it too)
         extra = {} if self.refiner_graphs is None else dict(refiner_graphs=bool(self.refiner_graphs))
+        if self.working_size is not None:
+            extra['working_size'] = self.working_size
         mdl = Tracker(augmenter, extractor, self.disc_params, refiner, self.device, feature_batch=self.feature_batch,
                       trunk_lanes=self.trunk_lanes, **extra)
         if self.weights is not None:
@@ -104,15 +109,19 @@ class Parameters:
         return mdl
 
 
-    def get_stream_pool(self, max_streams=8, grouped_apply=False, min_pairs=None, ragged_groups=False):
+    def get_stream_pool(self, max_streams=8, grouped_apply=False, min_pairs=None, ragged_groups=False, working_size=None):
         """A StreamPool (model/stream_pool.py) over the modules get_model() builds: one augmenter, trunk and refiner for up to
         ``max_streams`` live streams, each with target models of its own.  ``ragged_groups``: streams with different object counts share
-        one refiner pass and one merge (StreamPool's option of that name)."""
+        one refiner pass and one merge (StreamPool's option of that name).  ``working_size``: all streams are tracked at this size and
+        share one trunk pass per tick (StreamPool's option of that name; None: this object's ``working_size``)."""
         from .model.stream_pool import StreamPool
         if torch.device(self.device).type != 'cuda':
             raise RuntimeError('get_stream_pool: device %s; the FRTM hot path runs on the GPU only (no CPU fallback)' % (self.device,))
         mdl = self.get_model()
         extra = {} if min_pairs is None else dict(min_pairs=int(min_pairs))
+        working_size = self.working_size if working_size is None else working_size
+        if working_size is not None:
+            extra['working_size'] = working_size
         return StreamPool(mdl.augmenter, mdl.feature_extractor, self.disc_params, mdl.refiner, self.device, max_streams=max_streams,
                           grouped_apply=grouped_apply, trunk_lanes=self.trunk_lanes, ragged_groups=ragged_groups, **extra)
 
@@ -151,10 +160,15 @@ def parse_args(argv=None):
     ap.add_argument('--no-cpu-pin', action='store_true', help='leave the host threads to the scheduler instead of pinning them to cores near the GPU')
     ap.add_argument('--refiner-graphs', action='store_true', help='replay refiner windows as hipGraphs (Tracker(refiner_graphs=True); default: kernel by kernel, deep levels on a side stream)')
     ap.add_argument('--pull-push-fill', action='store_true', help="first-frame hole fill by the device-side pull-push pyramid (rounds 2-5) instead of Telea's fast-marching method on the host (the reference's cv2.inpaint recipe restated, the default)")
+    ap.add_argument('--working-size', type=int, nargs=2, default=None, metavar=('H', 'W'),
+                    help='track at this size: frames of any other size are resized to it on the device, label maps come back at native size '
+                         '(Tracker(working_size=(H, W)); default: frames are tracked at the size they arrive in; not with --ytvos-merge)')
     ap.add_argument('--keep-gc', action='store_true', help="leave Python's cyclic collector alone (default: held off while a sequence is enqueued)")
     args = ap.parse_args(argv)
     if args.ytvos_fork:
         args.ytvos_solver, args.ytvos_merge, args.upsampler = True, True, 'bicubic'
+    if args.working_size is not None:
+        args.working_size = tuple(args.working_size)
     return args
 
 
@@ -162,7 +176,8 @@ def parameters_from_args(args, weights):
     """Parameters of a parsed command line (main); the checkpoint `weights` as loaded from --model."""
     return Parameters(weights, fast=args.fast, device=args.dev, ytvos_fork_solver=args.ytvos_solver,
                       refiner_graphs=True if args.refiner_graphs else None, aug_fill='pull_push' if args.pull_push_fill else 'telea',
-                      upsampler=args.upsampler, trunk_precision=args.trunk_precision, refiner_precision=args.refiner_precision)
+                      upsampler=args.upsampler, trunk_precision=args.trunk_precision, refiner_precision=args.refiner_precision,
+                      working_size=getattr(args, 'working_size', None))
 
 
 def main(argv=None):

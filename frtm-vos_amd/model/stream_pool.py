@@ -27,16 +27,18 @@ TickBatch = namedtuple('TickBatch', 'size order groups fallbacks')
 TickPlan = namedtuple('TickPlan', 'batches skipped')
 
 
-def plan_tick(entries):
+def plan_tick(entries, working_size=None):
     """The plan of one tick, a pure function of ``entries`` = (sid, frame size, number of active objects, eligible) per stream named.
 
     -> TickPlan(batches, skipped).  One TickBatch per frame size (sizes in ascending order): ``order`` = the sids in trunk-batch order,
     ``groups`` = (start, g, n): the g streams order[start:start + g] have n active objects each and take the fused step together --
     contiguous in batch order, so their taps are one slice --, ``fallbacks`` = the batch indices of the streams that run their own
     ``track()`` on their slice of the taps (ineligible: an object starts on this frame, host-side guards, a raw log).  ``skipped`` =
-    streams without an active object: they take no part in the tick.  The result does not depend on the order of ``entries``."""
+    streams without an active object: they take no part in the tick.  The result does not depend on the order of ``entries``.
+    ``working_size``: every stream is tracked at this size whatever the size of its frames, so all streams form ONE TickBatch."""
     by_size, skipped = {}, []
     for sid, size, n, eligible in entries:
+        size = size if working_size is None else working_size
         if n <= 0:
             skipped.append(sid)
             continue
@@ -60,14 +62,15 @@ def plan_tick(entries):
     return TickPlan(batches, sorted(skipped))
 
 
-def plan_tick_ragged(entries):
+def plan_tick_ragged(entries, working_size=None):
     """plan_tick for a pool with ``ragged_groups``: the same batches, order, fallbacks and skipped streams, but ONE group per frame size,
     (start, g, counts): ALL eligible streams of the size, order[start:start + g], take the fused step together whatever their object
     counts -- counts[i] active objects on stream i of the group, ascending, since the order is by count and then by sid.  A stream with
     more than 15 active objects (the merge kernel's bound, ops.MAX_MERGE_OBJECTS) is a fallback.  Pure, and independent of the order of
-    ``entries``, like plan_tick."""
+    ``entries``, like plan_tick; ``working_size`` as there."""
     by_size, skipped = {}, []
     for sid, size, n, eligible in entries:
+        size = size if working_size is None else working_size
         if n <= 0:
             skipped.append(sid)
             continue
@@ -91,7 +94,7 @@ class _Stream:
 class StreamPool:
 
     def __init__(self, augmenter, feature_extractor, disc_params, refiner, device, max_streams=8, grouped_apply=False, min_pairs=2,
-                 trunk_lanes=2, ragged_groups=False):
+                 trunk_lanes=2, ragged_groups=False, working_size=None):
         """One augmenter, one trunk and one refiner for up to ``max_streams`` per-stream Tracker states built over those same modules.
         grouped_apply  True: the groups' target models score through ONE ops.target_apply_grouped launch pair; False: per pair
                        ``Discriminator.apply(ft, interleave=...)`` (three small launches each) -- the A/B of tools/stream_pool_time.py.
@@ -108,7 +111,12 @@ class StreamPool:
                        without the option.  False (default): streams share a pass only when their object counts are equal (plan_tick) -- same
                        launches, same bits as before the option existed.  Measured at 480x854 / RN101 (profiles/stream_pool_ragged_time.txt):
                        8 streams with 1, 1, 2, 2, 3, 3, 4 and 5 objects 14.59 -> 12.68 ms per tick against a max - min of 0.33 ms, 4 streams
-                       with 1 .. 4 objects 8.87 -> 7.16 ms, nothing on equal counts; one measurement introduces the option, the default waits."""
+                       with 1 .. 4 objects 8.87 -> 7.16 ms, nothing on equal counts; one measurement introduces the option, the default waits.
+        working_size   (h, w): every stream is tracked at this size whatever the size of its frames (Tracker's option of that name), so ALL
+                       streams of a tick share one trunk pass and the group rules above: the frames are packed into one staging buffer and
+                       resized by one launch (csrc/frame_resize.hip), and each group's masks go back to every stream's native size in one
+                       launch (ops.masks_to_native).  step() then answers at native size; the streams' state stays at the working size.
+                       None (default): one trunk pass per frame size -- same launches, same bits as before the option existed."""
         if torch.device(device).type != 'cuda':
             raise RuntimeError('StreamPool: device %s; the FRTM hot path runs on the GPU only (no CPU fallback)' % (device,))
         if int(max_streams) < 1:
@@ -120,6 +128,7 @@ class StreamPool:
         self.min_pairs = int(min_pairs)
         self.trunk_lanes = int(trunk_lanes)
         self.ragged_groups = bool(ragged_groups)
+        self.working_size = None if working_size is None else (int(working_size[0]), int(working_size[1]))
         self._streams = {}
         self._next_sid = 0
         self._disc_pool = []            # released target models, shared by all streams (Tracker.release_targets)
@@ -128,12 +137,18 @@ class StreamPool:
         self._ragged = {}               # (counts, size) -> ops.RaggedTable: one table for the scoring, the refiner and the merge
         self.grouped_launches = 0       # ops.target_apply_grouped calls so far (diagnostics)
         self.refiner_passes = 0         # refiner calls made by groups so far (diagnostics)
+        self.trunk_passes = 0           # trunk calls made by step() so far (diagnostics)
+        self._plans = {}                # native sizes of a tick's batch, in order -> (ops.ResizePlan, staging buffer, byte offsets)
+        self._native = {}               # (group key, native sizes) -> [ops.NativeTable, labels, soft, object ids of the rows, their LUTs]
+        # sid -> (H, W) uint8 label map (object ids, as Tracker.native_labels) at native size, for the streams whose LAST step went the way back
+        # from the working size; a stream whose last step answered with its current_masks (frame at the working size, or no option) has no entry
+        self.native_labels = {}
 
     # ---- streams ------------------------------------------------------------------------------------------------------------
     def open(self):
         if len(self._streams) >= self.max_streams:
             raise RuntimeError('StreamPool: %d streams are open already (max_streams)' % self.max_streams)
-        tr = Tracker(self.augmenter, self.feature_extractor, self.disc_params, self.refiner, self.device)
+        tr = Tracker(self.augmenter, self.feature_extractor, self.disc_params, self.refiner, self.device, working_size=self.working_size)
         tr.eval()
         tr._disc_pool = self._disc_pool                 # one pool of recycled target models for all streams
         sid, self._next_sid = self._next_sid, self._next_sid + 1
@@ -175,10 +190,15 @@ class StreamPool:
     def step(self, frames):
         """Tracks one frame for every stream named: {sid: image (3,H,W) uint8} -> {sid: masks (n_obj + 1, H, W)}.  A stream without an
         active object (no target yet, or all of them start on this very frame) is skipped and absent from the result.  Every stream's
-        current_frame advances by one.  The masks are the streams' ``current_masks``: valid until that stream's next step, like track()'s."""
+        current_frame advances by one.  The masks are the streams' ``current_masks``: valid until that stream's next step, like track()'s.
+        Under ``working_size`` a stream whose frame has another size gets its masks at the frame's NATIVE size instead, from a buffer the
+        pool keeps (valid until that stream's next step as well; its label map in ``native_labels[sid]``), while its ``current_masks``
+        stays at the working size."""
         for sid in frames:
             if sid not in self._streams:
                 raise KeyError(sid)
+        for sid in frames:
+            self.native_labels.pop(sid, None)
         entries, active_of = [], {}
         for sid, image in frames.items():
             tr = self._streams[sid].tracker
@@ -186,7 +206,7 @@ class StreamPool:
                 tr._check_first_frame_fits()            # as track(): no frame is scored with a half-fitted model
             active = active_of[sid] = tr.active_targets()
             entries.append((sid, tuple(image.shape[-2:]), len(active), self._eligible(tr, active)))
-        plan = plan_tick_ragged(entries) if self.ragged_groups else plan_tick(entries)
+        plan = (plan_tick_ragged if self.ragged_groups else plan_tick)(entries, working_size=self.working_size)
         out = {}
         ext = self.feature_extractor
         for tb in plan.batches:
@@ -200,26 +220,92 @@ class StreamPool:
             for tb in plan.batches:
                 B = len(tb.order)
                 batch = self._buf('frames', (B, 3, tb.size), (B, 3) + tb.size, torch.uint8)
-                for k, sid in enumerate(tb.order):
-                    batch[k].copy_(frames[sid], non_blocking=True)
+                natives = tuple(tuple(frames[sid].shape[-2:]) for sid in tb.order)
+                if any(nat != tb.size for nat in natives):              # (only under working_size)
+                    self._resize_batch(tb, natives, frames, batch)
+                else:
+                    for k, sid in enumerate(tb.order):
+                        batch[k].copy_(frames[sid], non_blocking=True)
                 taps = ext(batch)                                       # ONE trunk pass for the streams of this size
+                self.trunk_passes += 1
                 for start, g, n in tb.groups:
-                    self._run_group(tb, start, g, n, taps, active_of, out)
+                    self._run_group(tb, start, g, n, taps, active_of, out, natives)
                 for k in tb.fallbacks:
                     sid = tb.order[k]
-                    out[sid] = self._streams[sid].tracker.track(batch[k], features=FrameTaps(taps, k))
+                    tr = self._streams[sid].tracker
+                    out[sid] = tr.track(batch[k], features=FrameTaps(taps, k))
+                    if natives[k] != tb.size:                           # its own way back, like Tracker.track on a native frame
+                        labels, soft = tr._to_native(tr.current_masks.unsqueeze(0), natives[k], tr._object_lut(), soft=True, keep=True)
+                        tr.native_labels, out[sid] = labels[0], soft[0]
+                        self.native_labels[sid] = labels[0, 0]
                 del taps                                                # no tap view outlives the tick: the next pass overwrites them
         for sid in frames:
             self._streams[sid].tracker.current_frame += 1
         return out
 
-    def _run_group(self, tb, start, g, n, taps, active_of, out):
+    def _resize_batch(self, tb, natives, frames, batch):
+        """The tick's frames, of any sizes, into ``batch`` (B,3,h,w) at the working size: copied into ONE packed staging buffer (16-byte
+        aligned offsets) and resized by ONE launch, mode 'area' (the identity, bit for bit, for a frame that has the working size)."""
+        plan = self._plans.get(natives)
+        if plan is None:
+            offs, o = [], 0
+            for Hn, Wn in natives:
+                offs.append(o)
+                o += (3 * Hn * Wn + 15) // 16 * 16
+            desc = torch.tensor([[offs[k], nat[0], nat[1], ops.RESIZE_MODES['area']] for k, nat in enumerate(natives)], dtype=torch.int64)
+            plan = self._plans[natives] = (ops.ResizePlan(desc, self.device), torch.empty(o, dtype=torch.uint8, device=self.device), offs)
+        rp, staging, offs = plan
+        for k, sid in enumerate(tb.order):
+            Hn, Wn = natives[k]
+            if frames[sid].dtype != torch.uint8:
+                raise TypeError('StreamPool: working_size resizes uint8 frames, got %s' % frames[sid].dtype)
+            staging[offs[k]:offs[k] + 3 * Hn * Wn].view(3, Hn, Wn).copy_(frames[sid], non_blocking=True)
+        rp.frames(staging, 3, tb.size, out=batch)
+
+    def _group_to_native(self, key, masks, sids, planes, natives, size, out):
+        """The streams of a group whose frames have another size than the working size get their masks at native size: ONE
+        ops.masks_to_native launch for the group, into buffers kept per (group, native sizes); ``planes[i]``: (first plane, K) of stream
+        i in ``masks``.  The streams' state (current_masks) stays at the working size."""
+        rows_of = [i for i in range(len(sids)) if natives[i] != size]
+        if not rows_of:
+            return
+        nkey = (key, tuple(natives))
+        ent = self._native.get(nkey)
+        if ent is None:
+            rows, lo, so, to = [], 0, 0, 0
+            for i in rows_of:
+                (a, K), (Hn, Wn) = planes[i], natives[i]
+                rows.append((a * size[0] * size[1], K, Hn, Wn, lo, so, to))
+                lo, so, to = lo + Hn * Wn, so + K * Hn * Wn, to + K
+            table = ops.NativeTable(rows, self.device)
+            ent = self._native[nkey] = [table, torch.empty(table.label_bytes, dtype=torch.uint8, device=self.device),
+                                        torch.empty(table.soft_elems, device=self.device), None, None]
+        # every row's LUT: plane -> object id of ITS stream (Tracker._object_lut's ids); uploaded again only when a stream's objects change
+        ids = tuple(i_ for i in rows_of for i_ in self._plane_ids(sids[i], planes[i][1]))
+        if ent[3] != ids:
+            ent[3], ent[4] = ids, H.upload(torch.tensor(ids, dtype=torch.uint8), self.device)
+        table, labels, soft, _, luts = ent
+        ops.masks_to_native(masks, table, labels, luts, soft=soft)
+        for r, i in enumerate(rows_of):
+            out[sids[i]] = table.soft_of(soft, r)
+            self.native_labels[sids[i]] = table.labels_of(labels, r)
+
+    def _plane_ids(self, sid, K):
+        """Object id of each of stream ``sid``'s K mask planes (plane 0: the background, id 0)."""
+        tr = self._streams[sid].tracker
+        tr._object_lut()                                # (refuses ids beyond 255)
+        ids = (0,) + tr._native_lut[0]
+        if len(ids) != K:
+            raise RuntimeError('StreamPool: stream %r has %d mask planes and %d objects' % (sid, K, len(ids) - 1))
+        return ids
+
+    def _run_group(self, tb, start, g, n, taps, active_of, out, natives=None):
         """The fused step (model/tracker.py: fused_step) for g streams of n objects at once, one frame each, on the pool's buffers:
         pair p = i * n + k is (stream i of the group, its object k).  n a tuple (plan_tick_ragged): stream i carries n[i] objects."""
         self.refiner_passes += 1
         if isinstance(n, tuple):
             if len(set(n)) > 1:
-                return self._run_ragged_group(tb, start, n, taps, active_of, out)
+                return self._run_ragged_group(tb, start, n, taps, active_of, out, natives)
             n = n[0]                                    # equal counts: exactly the uniform group
         key = (g, n, tb.size)
         sids = tb.order[start:start + g]
@@ -240,8 +326,10 @@ class StreamPool:
             st.tracker.current_masks = masks[i]
             st.pool_masks = True
             out[sid] = masks[i]
+        if natives is not None and self.working_size is not None:
+            self._group_to_native(key, masks, sids, [(i * (n + 1), n + 1) for i in range(g)], natives[start:start + g], tb.size, out)
 
-    def _run_ragged_group(self, tb, start, counts, taps, active_of, out):
+    def _run_ragged_group(self, tb, start, counts, taps, active_of, out, natives=None):
         """_run_group for streams with different object counts: pairs stream-major, stream i's masks the planes table.planes(i) of ONE
         packed merge buffer.  Buffers and tables are kept per (counts, size): steady ticks allocate nothing."""
         key = (counts, tb.size)
@@ -268,3 +356,5 @@ class StreamPool:
             st.tracker.current_masks = masks[a:b]
             st.pool_masks = True
             out[sid] = masks[a:b]
+        if natives is not None and self.working_size is not None:
+            self._group_to_native(key, masks, sids, [(table.planes(i)[0], counts[i]  + 1) for i in range(g)], natives[start:start + g], tb.size, out)

@@ -266,8 +266,23 @@ class TargetObject:
 
 class Tracker(nn.Module):
 
-    def __init__(self, augmenter, feature_extractor, disc_params, refiner, device, feature_batch=16, trunk_lanes=2, refiner_graphs=False):
+    def __init__(self, augmenter, feature_extractor, disc_params, refiner, device, feature_batch=16, trunk_lanes=2, refiner_graphs=False,
+                 working_size=None):
         super().__init__()
+        # working_size (h, w): frames of any other size are resized to it on the device (mode 'area', csrc/frame_resize.hip; the first-frame
+        # label map nearest), every step and all state (current_masks, memories, target models) live at that size, and track() /
+        # run_sequence answer at the frame's native size (ops.masks_to_native, csrc/native_size.hip).  None (default): every path, launch
+        # and bit as without the option; so is a frame that already has the working size.
+        if working_size is not None:
+            working_size = tuple(int(v) for v in working_size)
+            if len(working_size) != 2 or not all(1 <= v <= ops.MAX_NATIVE_DIM for v in working_size):
+                raise ValueError('working_size must be (h, w) with 1 <= h, w <= %d, got %r' % (ops.MAX_NATIVE_DIM, working_size))
+        self.working_size = working_size
+        self._resize_plans = {}          # (kind, frames, native size) -> (ops.ResizePlan, output buffer or None)
+        self._native_tables = {}         # (frames, planes, native size, soft) -> ops.NativeTable
+        self._native_bufs = {}           # (planes, native size) -> (labels, soft): what track() answers with, valid until its next call
+        self._native_lut = None          # (object ids, device uint8 LUT) of track()'s native label map
+        self.native_labels = None        # track() under working_size: the (1, H, W) uint8 label map of the frame at its native size
         self.feature_batch = feature_batch
         self.trunk_lanes = trunk_lanes   # concurrent sub-batches of a trunk pass (frtm_backbone_set_lanes)
         self.graph_trunk = False         # trunk passes replayed as hipGraphs: nothing to gain since the host no longer waits for the GPU
@@ -395,6 +410,72 @@ class Tracker(nn.Module):
         self.current_frame = 0
         self.current_masks = None
         self.num_objects = 0
+        self.native_labels = None
+
+    # ---- working size ------------------------------------------------------------------
+    def _off_size(self, image):
+        """Does this frame take the way in and back: is a working size set, and has the frame another size?"""
+        return self.working_size is not None and tuple(image.shape[-2:]) != self.working_size
+
+    def _step_size(self, image):
+        """The size the tracking step of this frame runs at."""
+        return self.working_size if self.working_size is not None else image.shape[-2:]
+
+    def _resize_in(self, images, keep=False):
+        """(B,3,H,W) uint8 frames of one native size -> (B,3,h,w) at the working size in ONE launch (mode 'area').  ``keep``: into a buffer
+        kept per (B, native size), valid until the next such call (the per-frame callers); else a fresh tensor."""
+        if images.dtype != torch.uint8:
+            raise TypeError('working_size: frames are uint8 (the resize kernel reads bytes), got %s' % images.dtype)
+        B, native = images.shape[0], tuple(images.shape[-2:])
+        key = ('frames', B, native, bool(keep))
+        plan = self._resize_plans.get(key)
+        if plan is None:
+            n = 3 * native[0] * native[1]
+            desc = torch.tensor([[i * n, native[0], native[1], ops.RESIZE_MODES['area']] for i in range(B)], dtype=torch.int64)
+            buf = torch.empty((B, 3) + self.working_size, dtype=torch.uint8, device=self.device) if keep else None
+            plan = self._resize_plans[key] = (ops.ResizePlan(desc, self.device), buf)
+        return plan[0].frames(images.to(self.device).contiguous().view(-1), 3, self.working_size, out=plan[1])
+
+    def _resize_first(self, image, labels):
+        """The first frame (or a later one on which objects start) and its label map at the working size: the frame 'area', the ids nearest."""
+        native = tuple(image.shape[-2:])
+        if not torch.is_tensor(labels) or labels.dtype != torch.uint8:
+            raise TypeError('working_size: the label map is a uint8 tensor (the resize kernel reads bytes), got %s' % getattr(labels, 'dtype', type(labels).__name__))
+        im = self._resize_in(image.reshape(1, 3, *native), keep=True).view(tuple(image.shape[:-2]) + self.working_size)
+        key = ('labels', 1, native, False)
+        plan = self._resize_plans.get(key)
+        if plan is None:
+            plan = self._resize_plans[key] = (ops.ResizePlan(torch.tensor([[0, native[0], native[1], 0]], dtype=torch.int64), self.device), None)
+        lb = plan[0].label_map(labels.to(self.device).contiguous().view(-1), self.working_size)
+        return im, lb.view(tuple(labels.shape[:-2]) + self.working_size)
+
+    def _object_lut(self):
+        """Device uint8 table mask plane -> object id of the objects known so far (plane 0: the background, id 0)."""
+        ids = tuple(int(t.object_id) for t in sorted(self.targets.values(), key=lambda t: t.index))
+        if self._native_lut is None or self._native_lut[0] != ids:
+            if any(not 0 <= i < 256 for i in ids):
+                raise ValueError('working_size: object ids are 0 .. 255 (uint8 label maps), got %r' % (ids,))
+            self._native_lut = (ids, H.upload(torch.tensor((0,) + ids, dtype=torch.uint8), self.device))
+        return self._native_lut[1]
+
+    def _to_native(self, masks, native, lut, soft, keep=False):
+        """Merged masks (F,K,h,w) at the working size -> (labels (F,1,H,W) uint8, soft (F,K,H,W) or None) at ``native`` in ONE launch
+        (ops.masks_to_native).  ``keep``: into buffers kept per shape, valid until the next such call; else fresh tensors."""
+        masks = masks.contiguous()
+        F_, K = masks.shape[:2]
+        native = (int(native[0]), int(native[1]))
+        key = (F_, K, native, bool(soft))
+        table = self._native_tables.get(key)
+        if table is None:
+            table = self._native_tables[key] = ops.NativeTable.packed(self.working_size, [(K,) + native] * F_, self.device, soft=soft, shared_lut=True)
+        bufs = self._native_bufs.get(key) if keep else None
+        if bufs is None:
+            bufs = (torch.empty(table.label_bytes, dtype=torch.uint8, device=self.device),
+                    torch.empty(table.soft_elems, device=self.device) if soft else None)
+            if keep:
+                self._native_bufs[key] = bufs
+        ops.masks_to_native(masks, table, bufs[0], lut, soft=bufs[1])
+        return bufs[0].view(F_, 1, *native), (bufs[1].view(F_, K, *native) if soft else None)
 
     # ------------------------------------------------------------------------------------
     def run_dataset(self, dataset, out_path, speedrun=False, restart=None, writer=None):
@@ -508,6 +589,8 @@ class Tracker(nn.Module):
         the per-object masks BEFORE the per-frame merge are kept for the whole sequence, the ground truth is re-inserted on every
         object's first frame, and ONE merge over the sequence (background = min(1 - p), soft-max of p / (1 - p), arg-max) gives the
         labels.  Tracking itself (scores, refinement, per-frame merge for the memory updates) is unchanged."""
+        if ytvos_merge and self.working_size is not None:
+            raise ValueError("run_sequence: ytvos_merge with working_size is not supported (the fork's sequence-level merge at native size)")
         self.eval()
         self._raw_log = [] if ytvos_merge else None
         self.object_ids = sequence.obj_ids
@@ -542,7 +625,10 @@ class Tracker(nn.Module):
             if window:
                 masks_w = self.track_window([im for im, _ in window], [ft for _, ft in window])
                 # (the merge kernel has decoded the labels on the way when all planes came from the refiner; else: the ATen form)
-                labels_w = self._window_labels if self._window_labels is not None else decode(masks_w)
+                if self._off_size(window[0][0]):             # native-size label maps of the whole window in one launch, no soft planes
+                    labels_w = self._to_native(masks_w, window[0][0].shape[-2:], object_ids, soft=False)[0]
+                else:
+                    labels_w = self._window_labels if self._window_labels is not None else decode(masks_w)
                 for f in range(labels_w.shape[0]):
                     outputs.append(labels_w[f])
                     self.current_frame += 1
@@ -631,7 +717,7 @@ class Tracker(nn.Module):
             return True
         if any(t.discriminator.frames_until_solve() <= length for t in active if t.discriminator.update_filters):
             return True
-        Hh, Ww = image.shape[-2:]
+        Hh, Ww = self._step_size(image)
         per_sample = 4 * 64 * (Hh // 2 + 1) * (Ww // 2 + 1)      # largest refiner activation of one sample (bytes)
         return (length + 1) * len(active) * per_sample > 0x7fffffff or length >= 64
 
@@ -721,6 +807,8 @@ class Tracker(nn.Module):
             i0 = bounds[bi][0]
             idx = list(range(*bounds[bi]))
             batch = self._frame_batch([frames[j][0] for j in idx])
+            if self._off_size(batch):
+                batch = self._resize_in(batch)               # the whole trunk batch to the working size in one launch
             st = on if on is not None else side
             if st is not None:
                 st.wait_stream(torch.cuda.current_stream())         # the input batch (and the previous use of this tap set)
@@ -791,7 +879,10 @@ class Tracker(nn.Module):
     @torch.no_grad()
     @H.roctx('initialize')
     def initialize(self, image, labels, new_objects):
-        """Reference tracker.py:165-191."""
+        """Reference tracker.py:165-191.  Under ``working_size`` a frame of another size and its label map are resized first: the
+        augmentation and the fits run at the working size, and so does the mask stack returned."""
+        if self._off_size(image):
+            image, labels = self._resize_first(image, labels)
         Hh, Ww = image.shape[-2:]
         self.current_masks = H.fill(torch.empty((len(self.targets) + len(new_objects) + 1, Hh, Ww), device=self.device), 0.0)
         lab8 = labels.reshape(Hh, Ww)
@@ -958,7 +1049,7 @@ class Tracker(nn.Module):
         (as one batched update per object when that is decided on the device).
         Returns the per-frame ``current_masks`` stacked: (W, n_obj+1, H, W)."""
         W = len(images)
-        im_size = images[0].shape[-2:]
+        im_size = self._step_size(images[0])
         first = taps[0]
         feats = {L: first.batch[L][first.k:first.k + W] for L in first.batch} if isinstance(first, FrameTaps) else first
         active = self.active_targets()
@@ -966,7 +1057,7 @@ class Tracker(nn.Module):
         if self.fused_tail(active):
             # (the score maps are written straight into the refiner's (frame, object) batch; the merge kernel decodes the labels on the way)
             masks, self._window_labels = fused_step(self.refiner, [active] * W, feats, im_size, self.disc_params.update_filters,
-                                                    windowed=True, lut=self._lut, single=self._single)
+                                                    windowed=True, lut=None if self._off_size(images[0]) else self._lut, single=self._single)
         else:
             masks = self._track_stepwise(active, feats, im_size, W, windowed=True)
         self.current_masks = masks[W - 1]
@@ -974,8 +1065,21 @@ class Tracker(nn.Module):
 
     @torch.no_grad()
     def track(self, image, features=None):
-        """Reference tracker.py:193-227.  ``features``: optional pre-computed taps of this frame (frames_with_features)."""
-        im_size = image.shape[-2:]
+        """Reference tracker.py:193-227.  ``features``: optional pre-computed taps of this frame (frames_with_features).  Under
+        ``working_size`` a frame of another size is resized, the step runs at the working size (``current_masks`` stays there) and the
+        answer is the (n_obj + 1, H, W) stack at the frame's native size, valid until the next call; ``native_labels`` is its label map."""
+        if self._off_size(image):
+            native = tuple(image.shape[-2:])
+            if features is None:                                   # (with the taps given, the image only names the native size)
+                image = self._resize_in(image.reshape(1, 3, *native), keep=True).view(tuple(image.shape[:-2]) + self.working_size)
+            self._track(image, features, self.working_size)
+            labels, soft = self._to_native(self.current_masks.unsqueeze(0), native, self._object_lut(), soft=True, keep=True)
+            self.native_labels = labels[0]
+            return soft[0]
+        self.native_labels = None                                  # (this frame's answer is current_masks itself)
+        return self._track(image, features, image.shape[-2:])
+
+    def _track(self, image, features, im_size):
         if self._unchecked_fits and not self._in_run_sequence:
             self._check_first_frame_fits()
         if features is None:

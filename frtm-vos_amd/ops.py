@@ -775,3 +775,131 @@ def resize_labels_u8(src, desc, size):
     """frtm_resize_labels_u8: label maps packed like the frames (one plane each), ``desc`` rows (offset, h, w, obj_id) -> (n, 1, H, W)
     uint8 = (label == obj_id) at F.interpolate(mode='nearest')'s source indices.  One launch, enqueued on the current stream."""
     return _resize_packed('frtm_resize_labels_u8', src, desc, 1, size)
+
+
+def resize_label_map_u8(src, desc, size):
+    """frtm_resize_label_map_u8: label maps packed like the frames (one plane each), ``desc`` rows (offset, h, w, 0) -> (n, 1, H, W) uint8
+    = the label at F.interpolate(mode='nearest')'s source indices, ids kept (resize_labels_u8 compares them with one id instead).  One
+    launch, enqueued on the current stream."""
+    return _resize_packed('frtm_resize_label_map_u8', src, desc, 1, size)
+
+
+class ResizePlan:
+    """A frame table of resize_frames_u8 / resize_labels_u8 / resize_label_map_u8 that is uploaded ONCE: those functions upload their table
+    on every call (H.upload: an allocation and a copy), which a per-frame caller (Tracker.track under working_size, a StreamPool tick)
+    should not pay.  ``desc`` as there: a CPU int64 (n, 4) table.  ``frames`` / ``labels`` / ``label_map`` are those three launches on the
+    kept table; ``out``: the caller's (n, planes, H, W) uint8 buffer (else allocated)."""
+
+    def __init__(self, desc, device):
+        if not isinstance(desc, torch.Tensor) or desc.is_cuda or desc.dtype != torch.int64 or desc.dim() != 2 or desc.shape[1] != 4 or desc.shape[0] < 1:
+            raise TypeError('ResizePlan: the frame table is a CPU int64 tensor of shape (n, 4), n >= 1')
+        self.desc = desc.contiguous().clone()                         # the host copy the library checks on every call: kept alive here
+        self.n = self.desc.shape[0]
+        self.table = H.upload(self.desc, device)
+
+    def _run(self, entry, src, planes, size, out):
+        if not isinstance(src, torch.Tensor) or not src.is_cuda:
+            raise RuntimeError('%s: the packed source is on %s; the resize kernels run on the GPU only (no CPU fallback)'
+                               % (entry, getattr(src, 'device', type(src).__name__)))
+        if src.dtype != torch.uint8 or src.dim() != 1:
+            raise TypeError('%s: expected a flat uint8 buffer, got %s %s' % (entry, src.dtype, tuple(src.shape)))
+        shape = (self.n, planes, int(size[0]), int(size[1]))
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=src.device)
+        elif out.dtype != torch.uint8 or tuple(out.shape) != shape or not out.is_cuda:
+            raise TypeError('%s: out must be a uint8 device tensor of shape %r, got %s %s' % (entry, shape, out.dtype, tuple(out.shape)))
+        args = (H.ptr(src), src.numel(), self.desc.data_ptr(), H.ptr(self.table), self.n) + ((planes,) if entry == 'frtm_resize_frames_u8' else ())
+        H.call(entry, *args, H.ptr(out), shape[2], shape[3])
+        return out
+
+    def frames(self, src, planes, size, out=None):
+        return self._run('frtm_resize_frames_u8', src, int(planes), size, out)
+
+    def labels(self, src, size, out=None):
+        return self._run('frtm_resize_labels_u8', src, 1, size, out)
+
+    def label_map(self, src, size, out=None):
+        return self._run('frtm_resize_label_map_u8', src, 1, size, out)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# The way back from a working size (csrc/native_size.hip; Tracker(working_size=...), StreamPool(working_size=...))
+# ----------------------------------------------------------------------------------------------------------------------
+MAX_NATIVE_DIM = 16384        # frtm_masks_to_native and the resize kernels: 1 .. 16384 pixels per axis
+
+
+class NativeTable:
+    """The frame table of masks_to_native, built once per (sizes, plane counts) and kept, like RaggedTable: ``rows`` a CPU int64 (n, 7)
+    tensor of (offset of the frame's first plane in the mask buffer, K planes, native H, native W, offset of its label map in the label
+    buffer, offset of its K planes in the soft buffer or -1, offset of its K-byte LUT), offsets in elements of the buffer they index.
+    Every K is 1 .. MAX_MERGE_OBJECTS + 1 and every native size 1 .. 16384 (ValueError otherwise, on the host); a row whose offsets leave
+    the buffers of a call is skipped by the kernel.  ``label_bytes`` / ``soft_elems`` / ``lut_bytes``: the smallest buffers that hold
+    every row's output."""
+
+    def __init__(self, rows, device):
+        rows = torch.as_tensor(rows, dtype=torch.int64)
+        if rows.dim() != 2 or rows.shape[1] != 7 or rows.shape[0] < 1 or rows.shape[0] > 65535:
+            raise ValueError('NativeTable: rows are (n, 7), 1 <= n <= 65535, got %r' % (tuple(rows.shape),))
+        self.rows = rows.contiguous().clone()
+        for i, (_, K, Hn, Wn, _, _, _) in enumerate(self.rows.tolist()):
+            if not 1 <= K <= MAX_MERGE_OBJECTS + 1:
+                raise ValueError('NativeTable: frame %d has %d planes (1 .. %d)' % (i, K, MAX_MERGE_OBJECTS + 1))
+            if not (1 <= Hn <= MAX_NATIVE_DIM and 1 <= Wn <= MAX_NATIVE_DIM):
+                raise ValueError('NativeTable: frame %d has native size %d x %d (1 .. %d)' % (i, Hn, Wn, MAX_NATIVE_DIM))
+        r = self.rows
+        self.n = r.shape[0]
+        self.label_bytes = int((r[:, 4] + r[:, 2] * r[:, 3]).max())
+        self.soft_elems = int(torch.where(r[:, 5] >= 0, r[:, 5] + r[:, 1] * r[:, 2] * r[:, 3], torch.zeros_like(r[:, 5])).max())
+        self.lut_bytes = int((r[:, 6] + r[:, 1]).max())
+        self.dev = H.upload(self.rows, device)
+
+    @classmethod
+    def packed(cls, size, frames, device, soft=True, shared_lut=False):
+        """The table of ``frames`` = (K, H, W) per frame whose planes lie one frame after the other in the mask buffer (a (F, K, h, w)
+        stack, or the packed buffer of track_merge_ragged) at the working ``size``, with label maps, soft planes (``soft``) and LUTs
+        packed in frame order as well; ``shared_lut``: every frame reads the LUT at offset 0 (frames of one sequence)."""
+        h, w = int(size[0]), int(size[1])
+        rows, mo, lo, so, to = [], 0, 0, 0, 0
+        for K, Hn, Wn in frames:
+            K, Hn, Wn = int(K), int(Hn), int(Wn)
+            rows.append((mo, K, Hn, Wn, lo, so if soft else -1, 0 if shared_lut else to))
+            mo, lo, so, to = mo + K * h * w, lo + Hn * Wn, so + K * Hn * Wn, to + K
+        return cls(rows, device)
+
+    def labels_of(self, labels, i):
+        """Frame i's (H, W) label map in the flat label buffer of a call."""
+        o, Hn, Wn = int(self.rows[i, 4]), int(self.rows[i, 2]), int(self.rows[i, 3])
+        return labels[o:o + Hn * Wn].view(Hn, Wn)
+
+    def soft_of(self, soft, i):
+        """Frame i's (K, H, W) planes in the flat soft buffer of a call."""
+        o, K, Hn, Wn = int(self.rows[i, 5]), int(self.rows[i, 1]), int(self.rows[i, 2]), int(self.rows[i, 3])
+        return soft[o:o + K * Hn * Wn].view(K, Hn, Wn)
+
+
+def masks_to_native(masks, table, labels, luts, soft=None, size=None):
+    """frtm_masks_to_native: ``masks`` merged masks (..., h, w) float32 at the working size -- or, with ``size`` = (h, w) given, a buffer
+    of any shape that holds the planes at the table's offsets --, read as one flat buffer through ``table``
+    (NativeTable) -> ``labels`` (flat uint8 device buffer: every frame's native-size label map through its K bytes of ``luts``, flat
+    uint8) and, for the rows that ask for them, the K native-size planes in ``soft`` (flat float32).  Per pixel: the bilinear sample of
+    every plane (F.interpolate(mode='bilinear', align_corners=False); the plane itself on equal sizes), label = lut[arg-max] where the
+    arg-max is an object above 0.5, else lut[0].  One launch for all frames, enqueued on the current stream.  -> (labels, soft)."""
+    if not isinstance(masks, torch.Tensor) or masks.dtype is not _F32 or (soft is not None and (not isinstance(soft, torch.Tensor) or soft.dtype is not _F32)):
+        _refuse('masks_to_native', 'masks and soft are float32', masks=masks, soft=soft)
+    for name, t in (('labels', labels), ('luts', luts)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
+            raise TypeError('masks_to_native: %s must be a uint8 tensor, got %s' % (name, t.dtype if isinstance(t, torch.Tensor) else type(t).__name__))
+    if masks.dim() < (2 if size is None else 1) or labels.dim() != 1 or luts.dim() != 1 or (soft is not None and soft.dim() != 1):
+        _refuse('masks_to_native', 'expected masks (..., h, w) and flat labels, luts and soft buffers', masks=masks, soft=soft)
+    if not isinstance(table, NativeTable):
+        raise TypeError('masks_to_native: table must be an ops.NativeTable, got %s' % type(table).__name__)
+    h, w = masks.shape[-2:] if size is None else (int(size[0]), int(size[1]))
+    if not (1 <= h <= MAX_NATIVE_DIM and 1 <= w <= MAX_NATIVE_DIM):
+        raise ValueError('masks_to_native: working size %d x %d (1 .. %d)' % (h, w, MAX_NATIVE_DIM))
+    if soft is None and table.soft_elems > 0:
+        raise ValueError('masks_to_native: the table asks for soft planes, but there is no soft buffer')
+    if not (masks.is_cuda and labels.is_cuda and luts.is_cuda and (soft is None or soft.is_cuda)):
+        raise RuntimeError('masks_to_native: tensors on %s; the kernel runs on the GPU only (no CPU fallback)' % (masks.device,))
+    H.call('frtm_masks_to_native', H.ptr(masks), masks.numel(), int(h), int(w), table.rows.data_ptr(), H.ptr(table.dev), table.n,
+           H.ptr(labels), labels.numel(), H.ptr(soft), 0 if soft is None else soft.numel(), H.ptr(luts), luts.numel())
+    return labels, soft

@@ -736,6 +736,27 @@ int frtm_resize_frames_u8(const unsigned char* src, size_t src_bytes, const long
 int frtm_resize_labels_u8(const unsigned char* src, size_t src_bytes, const long long* desc_host, const long long* desc_dev, int n,
                           unsigned char* out, int H, int W, frtm_stream_t stream);
 
+/* The way back from a working size (csrc/native_size.hip; Tracker(working_size=...), StreamPool(working_size=...)): native-size label
+ * maps and masks from MERGED mask stacks at the working size h x w, for n frames of any native sizes and plane counts in one launch.
+ * masks: DEVICE fp32 buffer of mask_elems floats.  The table has one row of seven 64-bit words per frame and is passed twice like the
+ * resize tables (table_host is checked and sizes the grid, table_dev is what the kernel reads):
+ *   {offset of the frame's first plane in masks (floats), K planes (1 .. 16 = n_obj + 1), native H, native W (1 .. 16384 each),
+ *    offset of the frame's H x W label map in labels (bytes), offset of its K x H x W planes in soft (floats) or -1: none,
+ *    offset of its K-byte LUT in luts (bytes)}.
+ * Per native pixel: m_k = the bilinear sample of plane k (ATen's upsample_bilinear2d, align_corners=False; the plane itself when the sizes
+ * agree), arg = the first k with the largest m_k, label = lut[arg] if arg >= 1 and m_arg > 0.5f, else lut[0]; the soft planes are the m_k.
+ * On equal sizes the labels are frtm_track_merge's, byte for byte.  K or a native size outside its range returns FRTM_ERR_ARG without
+ * launching; a row whose frame does not lie inside the four buffers (mask_elems, label_bytes, soft_elems, lut_bytes) is SKIPPED: nothing
+ * of it is read or written.  soft may be NULL when no row asks for planes.  n <= 65535. */
+int frtm_masks_to_native(const float* masks, size_t mask_elems, int h, int w, const long long* table_host, const long long* table_dev, int n,
+                         unsigned char* labels, size_t label_bytes, float* soft, size_t soft_elems, const unsigned char* luts, size_t lut_bytes,
+                         frtm_stream_t stream);
+
+/* frtm_resize_labels_u8 with the id kept: rows {offset, h, w, 0}; out (n, 1, H, W) uint8 = src at the source index of
+ * F.interpolate(mode='nearest') (the first-frame label map on its way to the working size). */
+int frtm_resize_label_map_u8(const unsigned char* src, size_t src_bytes, const long long* desc_host, const long long* desc_dev, int n,
+                             unsigned char* out, int H, int W, frtm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
