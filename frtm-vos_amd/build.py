@@ -25,7 +25,7 @@ def _stale(target, deps):
 
 
 def build(force=False, verbose=True):
-    headers = [os.path.join(CSRC, 'frtm_common.h'), os.path.join(CSRC, 'conv_common.h'), os.path.join(CSRC, 'resident_grid.h'), os.path.join(CSRC, 'resample_taps.h'), os.path.join(CSRC, 'trunk_route.h'), os.path.join(os.path.dirname(HERE), 'include', 'frtm_hip.h'), __file__]
+    headers = [os.path.join(CSRC, 'frtm_common.h'), os.path.join(CSRC, 'conv_common.h'), os.path.join(CSRC, 'resident_grid.h'), os.path.join(CSRC, 'resample_taps.h'), os.path.join(CSRC, 'trunk_route.h'), os.path.join(CSRC, 'per_frame.h'), os.path.join(os.path.dirname(HERE), 'include', 'frtm_hip.h'), __file__]
     objs = []
     for src in SOURCES:
         sp = os.path.join(CSRC, src)

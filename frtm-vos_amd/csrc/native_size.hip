@@ -12,6 +12,7 @@
 // on equal sizes the labels are byte for byte frtm_track_merge's.
 #include "frtm_common.h"
 #include "resample_taps.h"
+#include "per_frame.h"       // MERGE_MAX: the planes of one merged frame
 #include "../../include/frtm_hip.h"
 #include <cstdint>
 
@@ -20,7 +21,6 @@
 #define NS_PR 36            // source rows per staged chunk: a tile that enlarges, or reduces by up to 2, is ONE chunk (16 * 2 + 2 rows)
 #define NS_PC 132           // source columns per staged chunk (64 * 2 + 2), + 1 word of padding per LDS row
 #define NS_PCP (NS_PC + 1)
-#define NS_KMAX 16          // MERGE_MAX of target_model.hip
 #define NS_MAXDIM 16384     // FR_MAXDIM of frame_resize.hip
 #define NS_ROW 7            // 64-bit words per table row
 
@@ -28,7 +28,7 @@
 __host__ __device__ static inline bool ns_row_ok(const long long* r, int h, int w, long long mask_elems, long long label_bytes, long long soft_elems,
                                                   long long lut_bytes) {
   const long long moff = r[0], K = r[1], H = r[2], W = r[3], loff = r[4], soff = r[5], toff = r[6];
-  if (K < 1 || K > NS_KMAX || H < 1 || W < 1 || H > NS_MAXDIM || W > NS_MAXDIM) return false;
+  if (K < 1 || K > MERGE_MAX || H < 1 || W < 1 || H > NS_MAXDIM || W > NS_MAXDIM) return false;
   if (moff < 0 || moff > mask_elems || K * h * w > mask_elems - moff) return false;
   if (loff < 0 || loff > label_bytes || H * W > label_bytes - loff) return false;
   if (soff != -1 && (soff < 0 || soff > soft_elems || K * H * W > soft_elems - soff)) return false;
@@ -146,7 +146,7 @@ extern "C" int frtm_masks_to_native(const float* masks, size_t mask_elems, int h
   int maxH = 0, maxW = 0;
   for (int i = 0; i < n; ++i) {
     const long long* r = table_host + (size_t)NS_ROW * i;
-    FRTM_CHECK_ARG(r[1] >= 1 && r[1] <= NS_KMAX, "frtm_masks_to_native: frame %d has %lld planes (1 .. %d)", i, r[1], NS_KMAX);
+    FRTM_CHECK_ARG(r[1] >= 1 && r[1] <= MERGE_MAX, "frtm_masks_to_native: frame %d has %lld planes (1 .. %d)", i, r[1], MERGE_MAX);
     FRTM_CHECK_ARG(r[2] >= 1 && r[3] >= 1 && r[2] <= NS_MAXDIM && r[3] <= NS_MAXDIM, "frtm_masks_to_native: frame %d has native size %lld x %lld (1 .. %d)",
                    i, r[2], r[3], NS_MAXDIM);
     FRTM_CHECK_ARG(r[5] == -1 || soft, "frtm_masks_to_native: frame %d asks for soft planes, but there is no soft buffer", i);

@@ -4,6 +4,7 @@
 // element-wise work, one kernel each instead of 5-10 framework launches.
 #include "frtm_common.h"
 #include "resample_taps.h"
+#include "per_frame.h"
 #include "../../include/frtm_hip.h"
 
 // out[pl] = bilinear(in[pl], (h,w) -> (H,W)) for `planes` maps.  One thread per output pixel computes the four taps once and
@@ -26,129 +27,26 @@ __global__ __launch_bounds__(256) void k_bilinear_resize(const float* __restrict
   }
 }
 
-// TSE score injection (seg_network.py:16-21: h = cat(reduce(ft), interpolate(score)); transform[0]; relu).  The 3x3 conv over
-// the 64 feature channels does not depend on the object and arrives pre-computed in `base` (C,H,W); this kernel adds the
-// contribution of the one score channel, the bias and the ReLU:
-//   out[n,c,y,x] = relu(base[c,y,x] + bias[c] + sum_{dy,dx} ws[c,dy,dx] * S_n(y+dy-1, x+dx-1)),  S_n = bilinear(scores[n]) (0 outside)
-#define INJ_TH 8       // tile = 8 rows x 32 columns: every half wave writes a 128-byte row segment (16 x 16 tiles: 64-byte segments, 46 us
-#define INJ_TW 32      // for the 120 x 214 level of 10 samples)
-#define INJ_CG 4      // channel groups per object (more workgroups on the small maps)
+// The per-frame glue -- TSE score injection, CAB gate, CAB combine -- with the frame of sample s found as s / group: the bodies, their
+// tiles and what they compute are in per_frame.h (the twins that read the frame from a table: ragged_group.hip).
 __global__ __launch_bounds__(256) void k_tse_inject(const float* __restrict__ base, const float* __restrict__ bias, const float* __restrict__ ws,
                                                      const float* __restrict__ scores, int C, int h, int w, int H, int W,
                                                      float* __restrict__ out, int group) {
-  __shared__ float S[INJ_TH + 2][INJ_TW + 2];
-  const int n = blockIdx.z / INJ_CG, cg = blockIdx.z % INJ_CG;
-  base += (size_t)(n / group) * C * H * W;                  // `group` consecutive samples (the objects of one frame) share a base map
-  const int cper = (C + INJ_CG - 1) / INJ_CG, c_lo = cg * cper, c_hi = min(C, c_lo + cper);
-  const int ty0 = blockIdx.y * INJ_TH, tx0 = blockIdx.x * INJ_TW;
-  const float* sc = scores + (size_t)n * h * w;
-  for (int i = threadIdx.x; i < (INJ_TH + 2) * (INJ_TW + 2); i += 256) {
-    const int r = i / (INJ_TW + 2), c = i % (INJ_TW + 2);
-    const int y = ty0 - 1 + r, x = tx0 - 1 + c;
-    S[r][c] = ((unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W) ? bilinear_at(sc, h, w, H, W, y, x) : 0.f;
-  }
-  __syncthreads();
-  const int ly = threadIdx.x / INJ_TW, lx = threadIdx.x % INJ_TW;
-  const int y = ty0 + ly, x = tx0 + lx;
-  if (y >= H || x >= W) return;
-  float s[9];
-#pragma unroll
-  for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-    for (int dx = 0; dx < 3; ++dx) s[dy * 3 + dx] = S[ly + dy][lx + dx];
-  const size_t HW = (size_t)H * W, pix = (size_t)y * W + x;
-  for (int c = c_lo; c < c_hi; ++c) {
-    float v = base[c * HW + pix] + bias[c];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) v += ws[c * 9 + k] * s[k];
-    out[((size_t)n * C + c) * HW + pix] = fmaxf(v, 0.f);
-  }
+  tse_inject_body(base, bias, ws, scores, FrameByGroup{group}, C, h, w, H, W, out);
 }
 
-// CAB combine (seg_network.py:38-41): out = shallower * sigmoid(gate[n,c]) + bilinear(deeper[n,c], (hd,wd) -> (H,W)).
 // deeper_group g > 0: samples s use deeper[s / g] (the pooled vector of the deepest level is shared by the objects of a frame);
 // g = 0: one deeper map per sample.
-#define CAB_RB 16      // rows of one plane per block: 64 x 4 threads, every thread 4 rows of its columns
 __global__ __launch_bounds__(256) void k_cab_combine(const float* __restrict__ shallow, const float* __restrict__ gate, const float* __restrict__ deeper,
                                                       int C, int hd, int wd, int deeper_group, int H, int W, float* __restrict__ out) {
-  // One block = CAB_RB rows of ONE plane: the sigmoid of the gate once per thread, the column taps once per column, the row taps once per
-  // row -- the element-wise form (64-bit index arithmetic, an exponential and both tap sets per element) ran at 2.1 TB/s on the
-  // 120 x 214 level.  Same expressions as bilinear_at, so the results are unchanged.
-  const int pl = blockIdx.y;                                // n * C + c
-  const int c = pl % C, n = pl / C;
-  const float g = 1.f / (1.f + __expf(-gate[pl]));
-  const size_t dn = deeper_group > 0 ? (size_t)(n / deeper_group) : (size_t)n;
-  const float* __restrict__ dp = deeper + (dn * C + c) * (size_t)hd * wd;
-  const float* __restrict__ sp = shallow + (size_t)pl * H * W;
-  float* __restrict__ op = out + (size_t)pl * H * W;
-  const bool same = (hd == H && wd == W);
-  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-  const int r0 = blockIdx.x * CAB_RB;
-  for (int x = tx; x < W; x += 64) {
-    int x0, x1; float lx0, lx1;
-    bilinear_taps(x, (float)wd / (float)W, wd, x0, x1, lx0, lx1);
-    float sv[CAB_RB / 4], dv[CAB_RB / 4];
-#pragma unroll
-    for (int k = 0; k < CAB_RB / 4; ++k) {                  // all loads of the thread's four rows first (independent), then the stores
-      const int y = min(r0 + ty + 4 * k, H - 1);
-      if (same) {
-        dv[k] = dp[y * wd + x];
-      } else {
-        int y0, y1; float ly0, ly1;
-        bilinear_taps(y, (float)hd / (float)H, hd, y0, y1, ly0, ly1);
-        dv[k] = ly0 * (lx0 * dp[y0 * wd + x0] + lx1 * dp[y0 * wd + x1]) + ly1 * (lx0 * dp[y1 * wd + x0] + lx1 * dp[y1 * wd + x1]);
-      }
-      sv[k] = sp[y * W + x];
-    }
-#pragma unroll
-    for (int k = 0; k < CAB_RB / 4; ++k) {
-      const int y = r0 + ty + 4 * k;
-      if (y < H) op[y * W + x] = sv[k] * g + dv[k];
-    }
-  }
+  cab_combine_body(shallow, gate, deeper, FrameByGroupOrOwn{deeper_group}, C, hd, wd, H, W, out);
 }
 
-
-// Channel-attention gate (seg_network.py:34-37): gate[n,:] = W2^T relu(W1^T [sp[n]; dp[n]] + b1) + b2 (the sigmoid is applied by
-// k_cab_combine).  sp / dp: pooled shallower / deeper features (n,oc); dp_stride = 0 broadcasts one deeper vector.  W1 (2oc,oc),
-// W2 (oc,oc) are the 1x1 conv weights transposed to [in][out].  One block per object: four framework launches (cat, addmm, relu,
-// addmm) become one.
+// dp_group as deeper_group of k_cab_combine.
 __global__ __launch_bounds__(256) void k_cab_gate(const float* __restrict__ sp, const float* __restrict__ dp, int dp_group,
                                                    const float* __restrict__ W1, const float* __restrict__ b1, const float* __restrict__ W2,
                                                    const float* __restrict__ b2, int oc, float* __restrict__ gate) {
-  extern __shared__ float sm[];                      // [2oc] input, [oc] hidden, [4][oc] partial sums
-  float* v = sm; float* hid = sm + 2 * oc; float* part = sm + 3 * oc;
-  const int n = blockIdx.x, tid = threadIdx.x;
-  const size_t dn = dp_group > 0 ? n / dp_group : n;
-  for (int i = tid; i < 2 * oc; i += 256) v[i] = i < oc ? sp[(size_t)n * oc + i] : dp[dn * oc + i - oc];
-  __syncthreads();
-  // each output is summed by 4 threads over a quarter of the inputs (independent loads in flight), then combined in fixed order
-  const int q = tid >> 6, lane = tid & 63;
-  for (int j0 = 0; j0 < oc; j0 += 64) {
-    const int j = j0 + lane;
-    const int i0 = q * (2 * oc / 4), i1 = (q + 1) * (2 * oc / 4);
-    float a = 0.f;
-    if (j < oc) {
-#pragma unroll 8
-      for (int i = i0; i < i1; ++i) a += v[i] * W1[(size_t)i * oc + j];
-      part[q * oc + j] = a;
-    }
-  }
-  __syncthreads();
-  for (int j = tid; j < oc; j += 256) hid[j] = fmaxf(b1[j] + ((part[j] + part[oc + j]) + (part[2 * oc + j] + part[3 * oc + j])), 0.f);
-  __syncthreads();
-  for (int k0 = 0; k0 < oc; k0 += 64) {
-    const int k = k0 + lane;
-    const int j0 = q * (oc / 4), j1 = (q + 1) * (oc / 4);
-    float a = 0.f;
-    if (k < oc) {
-#pragma unroll 8
-      for (int j = j0; j < j1; ++j) a += hid[j] * W2[(size_t)j * oc + k];
-      part[q * oc + k] = a;
-    }
-  }
-  __syncthreads();
-  for (int k = tid; k < oc; k += 256) gate[(size_t)n * oc + k] = b2[k] + ((part[k] + part[oc + k]) + (part[2 * oc + k] + part[3 * oc + k]));
+  cab_gate_body(sp, dp, FrameByGroupOrOwn{dp_group}, W1, b1, W2, b2, oc, gate);
 }
 
 // 2x polyphase bicubic up-sampling, replicate border (seg_network.py:75-126): out = crop1(interleave(conv4x4(pad2(in)))).

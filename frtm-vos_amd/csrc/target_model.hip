@@ -4,6 +4,7 @@
 // reductions with a fixed summation order (deterministic, no float atomics).
 #include "frtm_common.h"
 #include "resample_taps.h"
+#include "per_frame.h"
 #include "../../include/frtm_hip.h"
 
 // ------------------------------------------------------------------------------------------
@@ -771,7 +772,6 @@ __global__ __launch_bounds__(256) void k_transpose2d(const float* __restrict__ i
 // ------------------------------------------------------------------------------------------
 // Tracker.track mask merge (model/tracker.py:214-221) and the "fewer than 10 px" count (disc :214)
 // ------------------------------------------------------------------------------------------
-#define MERGE_MAX 16
 __global__ __launch_bounds__(256) void k_merge_masks(float* __restrict__ masks, int K, int HW) {
   masks += (size_t)blockIdx.y * K * HW;                      // blockIdx.y = frame of a window
   for (int i = blockIdx.x * 256 + threadIdx.x; i < HW; i += gridDim.x * 256) {
@@ -842,76 +842,12 @@ __global__ __launch_bounds__(256) void k_count_above(const float* __restrict__ m
   }
 }
 
-// ------------------------------------------------------------------------------------------
-// The tail of Tracker.track for a whole window of frames in ONE pass (reference model/tracker.py:200-221 + the label decoding of
-// run_sequence, :143-150 + the pixel counts Discriminator.update's early-out needs, discriminator.py:214):
-//   logits (W, n, HW) of the refiner  ->  sigmoid  ->  merge (clamp, background = min(1 - p), soft-max of p / (1 - p), arg-max keeps one
-//   plane)  ->  masks (W, n+1, HW)  +  counts[f][k] = #{masks > thr}  +  labels (W, HW) uint8 = lut[decode(masks)]
-// where decode is the reference's: one object: masks[1] > 0.5; several: the same merge applied to the MERGED masks, arg-max.
-// Replaces sigmoid + repeat + n plane copies + merge + count + clone + merge + argmax + index (ATen launches) of the window.
-// ------------------------------------------------------------------------------------------
+// The tail of Tracker.track for a whole window of frames in ONE pass, n objects in every frame: logits (W, n, HW) -> masks (W, n+1, HW),
+// counts (W, n+1), labels (W, HW).  The body is track_merge_body of per_frame.h (frames of different counts: ragged_group.hip).
 __global__ __launch_bounds__(256) void k_track_merge(const float* __restrict__ logits, int n, int HW, float* __restrict__ masks,
                                                      unsigned char* __restrict__ labels, const unsigned char* __restrict__ lut, int single,
                                                      int* __restrict__ counts, float thr) {
-  const int K = n + 1, f = blockIdx.y;
-  logits += (size_t)f * n * HW;
-  masks += (size_t)f * K * HW;
-  int cnt[MERGE_MAX];
-#pragma unroll
-  for (int k = 0; k < MERGE_MAX; ++k) cnt[k] = 0;
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < HW; i += gridDim.x * 256) {
-    float p[MERGE_MAX];
-    float bg = INFINITY;
-    for (int k = 1; k < K; ++k) {
-      const float x = logits[(size_t)(k - 1) * HW + i];
-      float v = 1.f / (1.f + expf(-x));                       // torch.sigmoid
-      v = fminf(fmaxf(v, 1e-7f), 1.f - 1e-7f);
-      p[k] = v;
-      bg = fminf(bg, 1.f - v);
-    }
-    p[0] = bg;
-    float mx = -INFINITY; int arg = 0;
-    for (int k = 0; k < K; ++k) { p[k] = p[k] / (1.f - p[k]); if (p[k] > mx) { mx = p[k]; arg = k; } }
-    float den = 0.f;
-    for (int k = 0; k < K; ++k) { p[k] = expf(p[k] - mx); den += p[k]; }
-    const float win = p[arg] / den;
-    for (int k = 0; k < K; ++k) masks[(size_t)k * HW + i] = (k == arg) ? win : 0.f;
-    if (win > thr) {
-#pragma unroll
-      for (int k = 0; k < MERGE_MAX; ++k) cnt[k] += (k == arg) ? 1 : 0;
-    }
-    if (labels) {
-      int lab;
-      if (single) lab = (arg == 1 && win > 0.5f) ? 1 : 0;     // :145  object_ids[(masks[1:2] > 0.5)]
-      else {
-        // :147-150 on the merged masks: every plane but `arg` is 0 -> 1e-7 after the clamp
-        const float v = fminf(fmaxf(win, 1e-7f), 1.f - 1e-7f), z = 1e-7f;
-        float b2 = INFINITY;
-        for (int k = 1; k < K; ++k) b2 = fminf(b2, 1.f - ((k == arg) ? v : z));
-        float m2 = -INFINITY; lab = 0;
-        for (int k = 0; k < K; ++k) {
-          const float q = (k == 0) ? b2 : ((k == arg) ? v : z);
-          const float o = q / (1.f - q);
-          if (o > m2) { m2 = o; lab = k; }
-        }
-      }
-      labels[(size_t)f * HW + i] = lut[lab];
-    }
-  }
-  if (counts) {
-    __shared__ int wsum[4][MERGE_MAX];
-    for (int k = 0; k < K; ++k) {
-      int c = cnt[k];
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off, 64);
-      if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6][k] = c;
-    }
-    __syncthreads();
-    if (threadIdx.x < K) {
-      const int tot = (wsum[0][threadIdx.x] + wsum[1][threadIdx.x]) + (wsum[2][threadIdx.x] + wsum[3][threadIdx.x]);
-      if (tot) atomicAdd(&counts[(size_t)f * K + threadIdx.x], tot);
-    }
-  }
+  track_merge_body(logits, UniformFrames{n}, HW, masks, labels, lut, single, counts, thr);
 }
 
 // ==========================================================================================
