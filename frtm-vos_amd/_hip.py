@@ -158,6 +158,7 @@ SIGNATURES = {
     'frtm_track_merge_ragged': (I, [P, I, P, I, P, P, F, P]),
     'frtm_masks_to_native': (I, [P, ctypes.c_size_t, I, I, P, P, I, P, ctypes.c_size_t, P, ctypes.c_size_t, P, ctypes.c_size_t, P]),
     'frtm_resize_label_map_u8': (I, [P, ctypes.c_size_t, P, P, I, P, I, I, P]),
+    'frtm_frames_to_rgb_u8': (I, [P, ctypes.c_size_t, P, P, I, P, I, I, P]),
 }
 
 _lib = None

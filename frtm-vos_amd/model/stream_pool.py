@@ -138,6 +138,8 @@ class StreamPool:
         self.grouped_launches = 0       # ops.target_apply_grouped calls so far (diagnostics)
         self.refiner_passes = 0         # refiner calls made by groups so far (diagnostics)
         self.trunk_passes = 0           # trunk calls made by step() so far (diagnostics)
+        self.frame_launches = 0         # ops.FramePlan launches made by step() so far: one per TickBatch that holds a DecoderFrame (diagnostics)
+        self._frame_plans = {}          # layouts of a tick's batch, in order -> (ops.FramePlan, staging buffer, byte offsets and counts)
         self._plans = {}                # native sizes of a tick's batch, in order -> (ops.ResizePlan, staging buffer, byte offsets)
         self._native = {}               # (group key, native sizes) -> [ops.NativeTable, labels, soft, object ids of the rows, their LUTs]
         # sid -> (H, W) uint8 label map (object ids, as Tracker.native_labels) at native size, for the streams whose LAST step went the way back
@@ -169,9 +171,12 @@ class StreamPool:
 
     @torch.no_grad()
     def initialize(self, sid, image, labels, new_objects):
-        """Tracker.initialize for stream ``sid``: the first frame, or objects that appear later; before step() on that frame."""
+        """Tracker.initialize for stream ``sid``: the first frame, or objects that appear later; before step() on that frame.  ``image``:
+        a (3,H,W) uint8 tensor or an ops.DecoderFrame."""
         st = self._streams[sid]
-        out = st.tracker.initialize(image.to(self.device), labels.to(self.device), new_objects)
+        if not isinstance(image, ops.DecoderFrame):
+            image = image.to(self.device)
+        out = st.tracker.initialize(image, labels.to(self.device), new_objects)
         st.pool_masks = False                           # (initialize() gives the stream a mask stack of its own)
         return out
 
@@ -188,7 +193,7 @@ class StreamPool:
 
     @torch.no_grad()
     def step(self, frames):
-        """Tracks one frame for every stream named: {sid: image (3,H,W) uint8} -> {sid: masks (n_obj + 1, H, W)}.  A stream without an
+        """Tracks one frame for every stream named: {sid: image (3,H,W) uint8 or ops.DecoderFrame} -> {sid: masks (n_obj + 1, H, W)}.  A stream without an
         active object (no target yet, or all of them start on this very frame) is skipped and absent from the result.  Every stream's
         current_frame advances by one.  The masks are the streams' ``current_masks``: valid until that stream's next step, like track()'s.
         Under ``working_size`` a stream whose frame has another size gets its masks at the frame's NATIVE size instead, from a buffer the
@@ -221,7 +226,9 @@ class StreamPool:
                 B = len(tb.order)
                 batch = self._buf('frames', (B, 3, tb.size), (B, 3) + tb.size, torch.uint8)
                 natives = tuple(tuple(frames[sid].shape[-2:]) for sid in tb.order)
-                if any(nat != tb.size for nat in natives):              # (only under working_size)
+                if any(isinstance(frames[sid], ops.DecoderFrame) for sid in tb.order):
+                    self._convert_batch(tb, frames, batch)
+                elif any(nat != tb.size for nat in natives):            # (only under working_size)
                     self._resize_batch(tb, natives, frames, batch)
                 else:
                     for k, sid in enumerate(tb.order):
@@ -261,6 +268,39 @@ class StreamPool:
                 raise TypeError('StreamPool: working_size resizes uint8 frames, got %s' % frames[sid].dtype)
             staging[offs[k]:offs[k] + 3 * Hn * Wn].view(3, Hn, Wn).copy_(frames[sid], non_blocking=True)
         rp.frames(staging, 3, tb.size, out=batch)
+
+    def _convert_batch(self, tb, frames, batch):
+        """_resize_batch for a tick that holds at least one ops.DecoderFrame, with or without a working size: every frame's bytes -- a
+        tensor's 3 h w, a decoder frame's nbytes_needed -- into ONE packed staging buffer (16-byte aligned offsets), and ONE ops.FramePlan
+        launch converts the NV12 rows, passes the planar ones on (format 'rgb') and takes all of them to the batch's size, mode 'area'."""
+        key = tuple(f.plan_key() if isinstance(f, ops.DecoderFrame) else tuple(f.shape[-2:]) for f in (frames[sid] for sid in tb.order))
+        plan = self._frame_plans.get(key)
+        if plan is None:
+            rows, spans, o = [], [], 0
+            for sid in tb.order:
+                f = frames[sid]
+                if isinstance(f, ops.DecoderFrame):
+                    rows.append(f.row(o, 'area'))
+                    nbytes = f.nbytes_needed
+                else:
+                    Hn, Wn = f.shape[-2:]
+                    rows.append([o, Hn, Wn, ops.RESIZE_MODES['area'], ops.FRAME_FORMATS['rgb'], 0, 0, 0])
+                    nbytes = 3 * Hn * Wn
+                spans.append((o, nbytes))
+                o += (nbytes + 15) // 16 * 16
+            plan = self._frame_plans[key] = (ops.FramePlan(torch.tensor(rows, dtype=torch.int64), self.device),
+                                             torch.empty(o, dtype=torch.uint8, device=self.device), spans)
+        fp, staging, spans = plan
+        for (o, nbytes), sid in zip(spans, tb.order):
+            f = frames[sid]
+            if isinstance(f, ops.DecoderFrame):
+                staging[o:o + nbytes].copy_(f.data[:nbytes], non_blocking=True)
+            else:
+                if f.dtype != torch.uint8:
+                    raise TypeError('StreamPool: a tick with decoder frames converts uint8 frames, got %s' % f.dtype)
+                staging[o:o + nbytes].view(f.shape[-3:]).copy_(f, non_blocking=True)
+        fp.frames(staging, tb.size, out=batch)
+        self.frame_launches += 1
 
     def _group_to_native(self, key, masks, sids, planes, natives, size, out):
         """The streams of a group whose frames have another size than the working size get their masks at native size: ONE

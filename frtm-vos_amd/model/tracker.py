@@ -264,6 +264,12 @@ class TargetObject:
         return self.discriminator.apply(ft, interleave=interleave)
 
 
+def _tensor_frames_only(who, images):
+    """The sequence paths read decoded files: their frames are tensors."""
+    if any(isinstance(im, ops.DecoderFrame) for im in images):
+        raise TypeError('%s takes tensor frames only; an ops.DecoderFrame goes through Tracker.initialize / track or a StreamPool' % who)
+
+
 class Tracker(nn.Module):
 
     def __init__(self, augmenter, feature_extractor, disc_params, refiner, device, feature_batch=16, trunk_lanes=2, refiner_graphs=False,
@@ -278,7 +284,7 @@ class Tracker(nn.Module):
             if len(working_size) != 2 or not all(1 <= v <= ops.MAX_NATIVE_DIM for v in working_size):
                 raise ValueError('working_size must be (h, w) with 1 <= h, w <= %d, got %r' % (ops.MAX_NATIVE_DIM, working_size))
         self.working_size = working_size
-        self._resize_plans = {}          # (kind, frames, native size) -> (ops.ResizePlan, output buffer or None)
+        self._resize_plans = {}          # (kind, frames, native size) -> (ops.ResizePlan, output buffer or None); ('decoder', size, pitch, uv offset, format) -> (ops.FramePlan, buffer)
         self._native_tables = {}         # (frames, planes, native size, soft) -> ops.NativeTable
         self._native_bufs = {}           # (planes, native size) -> (labels, soft): what track() answers with, valid until its next call
         self._native_lut = None          # (object ids, device uint8 LUT) of track()'s native label map
@@ -442,12 +448,30 @@ class Tracker(nn.Module):
         if not torch.is_tensor(labels) or labels.dtype != torch.uint8:
             raise TypeError('working_size: the label map is a uint8 tensor (the resize kernel reads bytes), got %s' % getattr(labels, 'dtype', type(labels).__name__))
         im = self._resize_in(image.reshape(1, 3, *native), keep=True).view(tuple(image.shape[:-2]) + self.working_size)
+        return im, self._resize_labels(labels, native)
+
+    def _resize_labels(self, labels, native):
+        """A uint8 label map at ``native`` size -> the working size, ids nearest."""
+        if not torch.is_tensor(labels) or labels.dtype != torch.uint8:
+            raise TypeError('working_size: the label map is a uint8 tensor (the resize kernel reads bytes), got %s' % getattr(labels, 'dtype', type(labels).__name__))
         key = ('labels', 1, native, False)
         plan = self._resize_plans.get(key)
         if plan is None:
             plan = self._resize_plans[key] = (ops.ResizePlan(torch.tensor([[0, native[0], native[1], 0]], dtype=torch.int64), self.device), None)
         lb = plan[0].label_map(labels.to(self.device).contiguous().view(-1), self.working_size)
-        return im, lb.view(tuple(labels.shape[:-2]) + self.working_size)
+        return lb.view(tuple(labels.shape[:-2]) + self.working_size)
+
+    def _decode(self, frame):
+        """An ops.DecoderFrame -> its (3, h, w) uint8 RGB planes at the step size in ONE launch (ops.FramePlan: colour conversion fused
+        into the resize, mode 'area'; at the frame's own size the conversion alone).  Plan and buffer are kept per (size, pitch, uv offset,
+        format): a steady loop allocates nothing, and the planes are valid until the next frame of that layout is decoded."""
+        size = tuple(int(v) for v in self._step_size(frame))
+        key = ('decoder',) + frame.plan_key()
+        plan = self._resize_plans.get(key)
+        if plan is None:
+            desc = torch.tensor([frame.row(0, 'area')], dtype=torch.int64)
+            plan = self._resize_plans[key] = (ops.FramePlan(desc, self.device), torch.empty((1, 3) + size, dtype=torch.uint8, device=self.device))
+        return plan[0].frames(frame.data, size, out=plan[1])[0]
 
     def _object_lut(self):
         """Device uint8 table mask plane -> object id of the objects known so far (plane 0: the background, id 0)."""
@@ -608,6 +632,7 @@ class Tracker(nn.Module):
         self._lut, self._single = object_ids, len(sequence.obj_ids) == 1
         if speedrun:
             image, labels, obj_ids = sequence[0]
+            _tensor_frames_only('run_sequence', [image])
             self.initialize(image.to(self.device), labels.to(self.device), sequence.obj_ids)
             self.track(image.to(self.device))
             torch.cuda.synchronize()
@@ -730,6 +755,7 @@ class Tracker(nn.Module):
         trunk kernels saturate the GPU either way).  Frame 0 of a sequence is never tracked (only initialised), so its taps
         are not computed."""
         frames = list(sequence)
+        _tensor_frames_only('frames_with_features', [f[0] for f in frames])
         fb = max(1, int(self.feature_batch))
         ext = self.feature_extractor
         also = [(self.refiner, 'use_graphs', self.graph_refiner)] if hasattr(self.refiner, 'use_graphs') else []
@@ -880,8 +906,13 @@ class Tracker(nn.Module):
     @H.roctx('initialize')
     def initialize(self, image, labels, new_objects):
         """Reference tracker.py:165-191.  Under ``working_size`` a frame of another size and its label map are resized first: the
-        augmentation and the fits run at the working size, and so does the mask stack returned."""
-        if self._off_size(image):
+        augmentation and the fits run at the working size, and so does the mask stack returned.  ``image`` may be an ops.DecoderFrame
+        (the label map stays a uint8 tensor at the picture's size): it is converted -- and resized, in the same launch -- first."""
+        if isinstance(image, ops.DecoderFrame):
+            if self._off_size(image):
+                labels = self._resize_labels(labels, tuple(image.shape[-2:]))
+            image = self._decode(image)
+        elif self._off_size(image):
             image, labels = self._resize_first(image, labels)
         Hh, Ww = image.shape[-2:]
         self.current_masks = H.fill(torch.empty((len(self.targets) + len(new_objects) + 1, Hh, Ww), device=self.device), 0.0)
@@ -1048,6 +1079,7 @@ class Tracker(nn.Module):
         Per frame the arithmetic is that of track(); the memory inserts and the re-solve run frame by frame afterwards, in order
         (as one batched update per object when that is decided on the device).
         Returns the per-frame ``current_masks`` stacked: (W, n_obj+1, H, W)."""
+        _tensor_frames_only('track_window', images)
         W = len(images)
         im_size = self._step_size(images[0])
         first = taps[0]
@@ -1067,17 +1099,24 @@ class Tracker(nn.Module):
     def track(self, image, features=None):
         """Reference tracker.py:193-227.  ``features``: optional pre-computed taps of this frame (frames_with_features).  Under
         ``working_size`` a frame of another size is resized, the step runs at the working size (``current_masks`` stays there) and the
-        answer is the (n_obj + 1, H, W) stack at the frame's native size, valid until the next call; ``native_labels`` is its label map."""
+        answer is the (n_obj + 1, H, W) stack at the frame's native size, valid until the next call; ``native_labels`` is its label map.
+        ``image`` may be an ops.DecoderFrame: one launch converts it and takes it to the step size, the rest is what a tensor frame gets."""
+        decoder = isinstance(image, ops.DecoderFrame)
         if self._off_size(image):
             native = tuple(image.shape[-2:])
-            if features is None:                                   # (with the taps given, the image only names the native size)
+            if decoder:
+                image = self._decode(image) if features is None else None
+            elif features is None:                                 # (with the taps given, the image only names the native size)
                 image = self._resize_in(image.reshape(1, 3, *native), keep=True).view(tuple(image.shape[:-2]) + self.working_size)
             self._track(image, features, self.working_size)
             labels, soft = self._to_native(self.current_masks.unsqueeze(0), native, self._object_lut(), soft=True, keep=True)
             self.native_labels = labels[0]
             return soft[0]
         self.native_labels = None                                  # (this frame's answer is current_masks itself)
-        return self._track(image, features, image.shape[-2:])
+        size = image.shape[-2:]
+        if decoder:
+            image = self._decode(image) if features is None else None
+        return self._track(image, features, size)
 
     def _track(self, image, features, im_size):
         if self._unchecked_fits and not self._in_run_sequence:

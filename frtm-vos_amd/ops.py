@@ -823,6 +823,115 @@ class ResizePlan:
 
 
 # ----------------------------------------------------------------------------------------------------------------------
+# Decoder frames: NV12 surfaces (and planar RGB) to planar RGB at one size in one launch (csrc/frame_formats.hip)
+# ----------------------------------------------------------------------------------------------------------------------
+FRAME_FORMATS = {'rgb': 0, 'nv12_bt601': 1, 'nv12_bt601_full': 2, 'nv12_bt709': 3, 'nv12_bt709_full': 4}
+
+
+def _frames_args(entry, src, desc):
+    if not isinstance(src, torch.Tensor) or not src.is_cuda:
+        raise RuntimeError('%s: the source buffer is on %s; the frame kernels run on the GPU only (no CPU fallback)'
+                           % (entry, getattr(src, 'device', type(src).__name__)))
+    if src.dtype != torch.uint8 or src.dim() != 1:
+        raise TypeError('%s: expected a flat uint8 buffer, got %s %s' % (entry, src.dtype, tuple(src.shape)))
+    if desc is not None and (not isinstance(desc, torch.Tensor) or desc.is_cuda or desc.dtype != torch.int64 or desc.dim() != 2
+                             or desc.shape[1] != 8 or desc.shape[0] < 1):
+        raise TypeError('%s: the frame table is a CPU int64 tensor of shape (n, 8), n >= 1' % entry)
+
+
+def frames_to_rgb_u8(src, desc, size):
+    """frtm_frames_to_rgb_u8: ``src`` a flat uint8 device buffer, ``desc`` a CPU int64 (n, 8) table of rows (offset, h, w,
+    RESIZE_MODES[mode], FRAME_FORMATS[format], pitch, uv offset, 0) -> (n, 3, H, W) uint8 planar RGB on the device: each frame converted by
+    the fixed-point formula of include/frtm_hip.h and put through resize_frames_u8's operator, bit for bit.  One launch, enqueued on the
+    current stream; the table is uploaded per call (FramePlan keeps it)."""
+    _frames_args('frtm_frames_to_rgb_u8', src, desc)
+    desc = desc.contiguous()
+    out = torch.empty(desc.shape[0], 3, int(size[0]), int(size[1]), dtype=torch.uint8, device=src.device)
+    table = H.upload(desc, src.device)
+    H.call('frtm_frames_to_rgb_u8', H.ptr(src), src.numel(), desc.data_ptr(), H.ptr(table), desc.shape[0], H.ptr(out), int(size[0]), int(size[1]))
+    return out
+
+
+class FramePlan:
+    """A frame table of frames_to_rgb_u8 that is uploaded ONCE (ResizePlan's role for that launch).  ``desc``: a CPU int64 (n, 8) table;
+    ``frames(src, size, out=None)``: the launch on the kept table, ``out`` the caller's (n, 3, H, W) uint8 buffer (else allocated)."""
+
+    def __init__(self, desc, device):
+        if not isinstance(desc, torch.Tensor) or desc.is_cuda or desc.dtype != torch.int64 or desc.dim() != 2 or desc.shape[1] != 8 or desc.shape[0] < 1:
+            raise TypeError('FramePlan: the frame table is a CPU int64 tensor of shape (n, 8), n >= 1')
+        self.desc = desc.contiguous().clone()                         # the host copy the library checks on every call: kept alive here
+        self.n = self.desc.shape[0]
+        self.table = H.upload(self.desc, device)
+
+    def frames(self, src, size, out=None):
+        entry = 'frtm_frames_to_rgb_u8'
+        _frames_args(entry, src, None)
+        shape = (self.n, 3, int(size[0]), int(size[1]))
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=src.device)
+        elif not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != shape or not out.is_cuda:
+            raise TypeError('%s: out must be a uint8 device tensor of shape %r, got %s %s'
+                            % (entry, shape, getattr(out, 'dtype', type(out).__name__), tuple(getattr(out, 'shape', ()))))
+        H.call(entry, H.ptr(src), src.numel(), self.desc.data_ptr(), H.ptr(self.table), self.n, H.ptr(out), shape[2], shape[3])
+        return out
+
+
+class DecoderFrame:
+    """One NV12 surface as a hardware video decoder leaves it on the device, accepted wherever Tracker.initialize / track and
+    StreamPool.initialize / step take a (3, H, W) uint8 frame.  ``data``: a flat uint8 CUDA tensor that STARTS at the Y plane (a view
+    over the surface's memory: nothing is copied here); ``height`` x ``width``: the picture, 1 .. 16384 each, odd sizes allowed; ``pitch``:
+    bytes from one row to the next in both planes (default 2 * ceil(width / 2): no padding); ``uv_offset``: byte offset of the interleaved
+    U,V plane in ``data`` (default pitch * height; a coded height above the picture's is expressed by passing pitch * coded height);
+    ``matrix`` 'bt601' or 'bt709', ``full_range``: which of the four conversions of include/frtm_hip.h applies.  Everything is
+    checked here, on the host; no GPU work is done before the frame is used."""
+
+    def __init__(self, data, height, width, pitch=None, uv_offset=None, matrix='bt709', full_range=False):
+        if not isinstance(data, torch.Tensor) or data.dtype != torch.uint8 or data.dim() != 1:
+            raise TypeError('DecoderFrame: data is a flat uint8 tensor, got %s %s'
+                            % (getattr(data, 'dtype', type(data).__name__), tuple(getattr(data, 'shape', ()))))
+        self.height, self.width = int(height), int(width)
+        self.pitch, self.uv_offset, self.nbytes_needed = self.layout(height, width, pitch, uv_offset)
+        name = 'nv12_%s%s' % (matrix, '_full' if full_range else '')
+        if matrix not in ('bt601', 'bt709') or name not in FRAME_FORMATS:
+            raise ValueError("DecoderFrame: matrix is 'bt601' or 'bt709', got %r" % (matrix,))
+        self.matrix, self.full_range = matrix, bool(full_range)
+        self.format = FRAME_FORMATS[name]
+        if data.numel() < self.nbytes_needed:
+            raise ValueError('DecoderFrame: data holds %d bytes, the surface needs %d' % (data.numel(), self.nbytes_needed))
+        if not data.is_cuda:
+            raise RuntimeError('DecoderFrame: data is on %s; a decoder surface lives on the GPU (no CPU fallback)' % data.device)
+        if not data.is_contiguous():
+            raise TypeError('DecoderFrame: data must be contiguous')
+        self.data = data
+        self.shape = torch.Size((3, self.height, self.width))
+        self.dtype = torch.uint8
+        self.device = data.device
+
+    @staticmethod
+    def layout(height, width, pitch=None, uv_offset=None):
+        """(pitch, uv_offset, nbytes_needed) of a surface with the defaults filled in; ValueError for a layout no surface has."""
+        height, width = int(height), int(width)
+        if not (1 <= height <= MAX_NATIVE_DIM and 1 <= width <= MAX_NATIVE_DIM):
+            raise ValueError('DecoderFrame: picture size %d x %d (1 .. %d)' % (height, width, MAX_NATIVE_DIM))
+        chroma_row = 2 * ((width + 1) // 2)
+        pitch = chroma_row if pitch is None else int(pitch)
+        if pitch < chroma_row:
+            raise ValueError('DecoderFrame: pitch %d is below the %d bytes of a chroma row' % (pitch, chroma_row))
+        uv_offset = pitch * height if uv_offset is None else int(uv_offset)
+        if uv_offset < pitch * height:
+            raise ValueError('DecoderFrame: uv_offset %d lies inside the Y plane (%d rows of pitch %d)' % (uv_offset, height, pitch))
+        return pitch, uv_offset, uv_offset + pitch * ((height + 1) // 2)
+
+    def row(self, offset=0, mode='area'):
+        """This frame's row of a frames_to_rgb_u8 table, its Y plane at byte ``offset`` of the source buffer."""
+        return [int(offset), self.height, self.width, RESIZE_MODES[mode], self.format, self.pitch, int(offset) + self.uv_offset, 0]
+
+    def plan_key(self):
+        """What a cached FramePlan of this frame depends on."""
+        return (self.height, self.width, self.pitch, self.uv_offset, self.format)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
 # The way back from a working size (csrc/native_size.hip; Tracker(working_size=...), StreamPool(working_size=...))
 # ----------------------------------------------------------------------------------------------------------------------
 MAX_NATIVE_DIM = 16384        # frtm_masks_to_native and the resize kernels: 1 .. 16384 pixels per axis

@@ -757,6 +757,34 @@ int frtm_masks_to_native(const float* masks, size_t mask_elems, int h, int w, co
 int frtm_resize_label_map_u8(const unsigned char* src, size_t src_bytes, const long long* desc_host, const long long* desc_dev, int n,
                              unsigned char* out, int H, int W, frtm_stream_t stream);
 
+/* Decoder frames to planar RGB at one output size, n frames of any sizes, formats and modes in ONE launch (csrc/frame_formats.hip):
+ * colour conversion and frtm_resize_frames_u8's operator fused.  src and the two copies of the table as there; a row is eight 64-bit words
+ *   {off, h, w, mode, format, pitch, uv_off, 0}.
+ * FRTM_FRAME_RGB: three planes of h x w bytes at off (pitch and uv_off ignored): exactly frtm_resize_frames_u8 with planes = 3.
+ * FRTM_FRAME_NV12_*: an NV12 surface -- Y plane at off, rows `pitch` bytes apart; interleaved U,V plane at uv_off (uv_off > off + pitch * h
+ * expresses a coded height above the picture's), rows `pitch` apart as well, pitch >= 2 * ceil(w / 2).  Source pixel (y, x):
+ *   Y = src[off + y * pitch + x], U = src[uv_off + (y >> 1) * pitch + 2 * (x >> 1)], V = the byte after U   (chroma replicated, not interpolated)
+ *   yy = Y - y0, u = U - 128, v = V - 128, in int32:
+ *   R = clamp(floor((a * yy + rv * v + 32768) / 65536), 0, 255)
+ *   G = clamp(floor((a * yy - gu * u - gv * v + 32768) / 65536), 0, 255)
+ *   B = clamp(floor((a * yy + bu * u + 32768) / 65536), 0, 255)
+ *   format            y0      a      rv     gu     gv      bu      (round(65536 * coefficient) of the standard matrices)
+ *   NV12_BT601        16  76309  104597  25675  53279  132201
+ *   NV12_BT601_FULL    0  65536   91881  22553  46802  116130
+ *   NV12_BT709        16  76309  117489  13975  34925  138438
+ *   NV12_BT709_FULL    0  65536  103206  12276  30679  121609
+ * out (n, 3, H, W) uint8 = those uint8 planes through frtm_resize_frames_u8's operator, bit for bit (H x W = h x w: the conversion alone).
+ * Loads touch [off, off + pitch * h) and [uv_off, uv_off + pitch * ceil(h / 2)) only ([off, off + 3 h w) for FRTM_FRAME_RGB), and of those
+ * only picture samples.  Refused with FRTM_ERR_ARG before any launch: a null pointer, n < 1, 3 n > 65535, a size outside 1 .. 16384, an
+ * unknown mode or format, pitch < 2 * ceil(w / 2), a range that leaves [0, src_bytes). */
+#define FRTM_FRAME_RGB 0
+#define FRTM_FRAME_NV12_BT601 1
+#define FRTM_FRAME_NV12_BT601_FULL 2
+#define FRTM_FRAME_NV12_BT709 3
+#define FRTM_FRAME_NV12_BT709_FULL 4
+int frtm_frames_to_rgb_u8(const unsigned char* src, size_t src_bytes, const long long* desc_host, const long long* desc_dev, int n,
+                          unsigned char* out, int H, int W, frtm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
