@@ -181,7 +181,8 @@ __global__ __launch_bounds__(256) void k_bn_apply_relu(const float* __restrict__
   out[o] = fmaxf((x[o] - mean[c]) * a + beta[c], 0.f);
 }
 
-// backward, pass 1: g = dy * (out > 0); part[(c * N + n) * 2 + {0, 1}] = sum g, sum g * xhat over plane (n, c)
+// backward, pass 1: g = dy * (out > 0); part[(c * N + n) * 3 + {0, 1, 2}] = sum g, sum g * xhat, sum xhat over plane (n, c).  The third sum is not
+// zero: xhat is centred on the fp32 mean, which lies up to half an ulp from the mean of x
 __global__ __launch_bounds__(256) void k_bn_bwd_part(const float* __restrict__ dy, const float* __restrict__ out, const float* __restrict__ x,
                                                       const float* __restrict__ mean, const float* __restrict__ invstd, int C, int HW,
                                                       double* __restrict__ part) {
@@ -189,26 +190,36 @@ __global__ __launch_bounds__(256) void k_bn_bwd_part(const float* __restrict__ d
   const int n = blockIdx.x, c = blockIdx.y, N = gridDim.x;
   const size_t o = ((size_t)n * C + c) * HW;
   const float m = mean[c], is = invstd[c];
-  double s = 0.0, q = 0.0;
+  double s = 0.0, q = 0.0, xs = 0.0, none = 0.0;
   for (int i = threadIdx.x; i < HW; i += 256) {
     const float g = out[o + i] > 0.f ? dy[o + i] : 0.f;
     s += g;
     q += (double)g * (double)((x[o + i] - m) * is);
+    xs += ((double)x[o + i] - (double)m) * (double)is;         // as k_bn_bwd_apply forms xhat
   }
   block_sum2_d(s, q, red);
-  if (threadIdx.x == 0) { part[((size_t)c * N + n) * 2] = s; part[((size_t)c * N + n) * 2 + 1] = q; }
+  block_sum2_d(xs, none, red);
+  if (threadIdx.x == 0) {
+    part[((size_t)c * N + n) * 3] = s;
+    part[((size_t)c * N + n) * 3 + 1] = q;
+    part[((size_t)c * N + n) * 3 + 2] = xs;
+  }
 }
 
 // backward, pass 2: every block sums its channel's partials in the same fixed order, then
-//   train: dx = gamma * invstd / cnt * (cnt * g - sum g - xhat * sum g xhat)      eval: dx = gamma * invstd * g
+//   train: dx = gamma * invstd / cnt * (cnt * g - sum g - (xhat - sum xhat / cnt) * sum g xhat)      eval: dx = gamma * invstd * g
 // and the first block of each channel writes dgamma = sum g xhat, dbeta = sum g.  grid (ceil(HW / 256), N * C)
 __global__ __launch_bounds__(256) void k_bn_bwd_apply(const float* __restrict__ dy, const float* __restrict__ out, const float* __restrict__ x,
                                                        const float* __restrict__ mean, const float* __restrict__ invstd,
                                                        const float* __restrict__ gamma, const double* __restrict__ part, int N, int C, int HW,
                                                        int train, float* __restrict__ dx, float* __restrict__ dgamma, float* __restrict__ dbeta) {
   const int i = blockIdx.x * 256 + threadIdx.x, pl = blockIdx.y, c = pl % C;
-  double s = 0.0, q = 0.0;
-  for (int n = 0; n < N; ++n) { s += part[((size_t)c * N + n) * 2]; q += part[((size_t)c * N + n) * 2 + 1]; }
+  double s = 0.0, q = 0.0, xs = 0.0;
+  for (int n = 0; n < N; ++n) {
+    s += part[((size_t)c * N + n) * 3];
+    q += part[((size_t)c * N + n) * 3 + 1];
+    xs += part[((size_t)c * N + n) * 3 + 2];
+  }
   if (blockIdx.x == 0 && pl == c && threadIdx.x == 0) {
     if (dgamma) dgamma[c] = (float)q;
     if (dbeta) dbeta[c] = (float)s;
@@ -220,9 +231,10 @@ __global__ __launch_bounds__(256) void k_bn_bwd_apply(const float* __restrict__ 
   if (train) {
     const double cnt = (double)N * HW;
     // in fp64 with one final rounding: fp32 copies of sum g / n and sum g xhat / n would put the same rounding into every element of the
-    // channel, and the conv bias in front, whose gradient is sum dx = 0 exactly, would collect it n times
+    // channel, and the conv bias in front, whose gradient is sum dx = 0 exactly, would collect it n times.  For the same reason xhat is
+    // re-centred by its own mean in the last term: the fp32 mean alone leaves sum dx = -gamma invstd^2 (sum g xhat) (mean of x - mean[c])
     const double xh = ((double)x[o] - (double)mean[c]) * (double)is;
-    dx[o] = (float)((double)gamma[c] * (double)is * ((double)g - s / cnt - xh * (q / cnt)));
+    dx[o] = (float)((double)gamma[c] * (double)is * ((double)g - s / cnt - (xh - xs / cnt) * (q / cnt)));
   } else {
     dx[o] = a * g;
   }

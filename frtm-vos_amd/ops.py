@@ -545,7 +545,7 @@ def bn_relu_backward(dy, out, x, mean, invstd, gamma, train, affine=True):
     dx = torch.empty_like(x)
     dg = torch.empty(C, device=x.device) if affine else None
     db = torch.empty(C, device=x.device) if affine else None
-    part = torch.empty(2 * N * C, device=x.device, dtype=torch.float64)
+    part = torch.empty(3 * N * C, device=x.device, dtype=torch.float64)
     H.call('frtm_bn_relu_backward', H.ptr(dy), H.ptr(out), H.ptr(x), H.ptr(mean), H.ptr(invstd), H.ptr(gamma), N, C, Hh * Ww, int(bool(train)),
            H.ptr(dx), H.ptr(dg), H.ptr(db), H.ptr(part))
     return dx, dg, db

@@ -591,8 +591,9 @@ int frtm_bn_stats(const float* x, int N, int C, int HW, float eps, float factor,
 /* out = relu((x - mean[c]) * invstd[c] * gamma[c] + beta[c]) */
 int frtm_bn_apply_relu(const float* x, const float* mean, const float* invstd, const float* gamma, const float* beta, int N, int C, int HW,
                        float* out, frtm_stream_t stream);
-/* Backward of frtm_bn_apply_relu: g = dy * (out > 0); train: dx = gamma*invstd/n * (n g - sum g - xhat sum g xhat) (in fp64, one rounding), eval: dx =
- * gamma*invstd*g; dgamma = sum g xhat, dbeta = sum g (either may be NULL).  part: >= 2*N*C doubles. */
+/* Backward of frtm_bn_apply_relu: g = dy * (out > 0); train: dx = gamma*invstd/n * (n g - sum g - (xhat - sum xhat / n) sum g xhat) (in fp64, one
+ * rounding; xhat is centred on the fp32 mean, its own mean is taken out so that sum dx vanishes), eval: dx = gamma*invstd*g; dgamma = sum g xhat,
+ * dbeta = sum g (either may be NULL).  part: >= 3*N*C doubles. */
 int frtm_bn_relu_backward(const float* dy, const float* out, const float* x, const float* mean, const float* invstd, const float* gamma,
                           int N, int C, int HW, int train, float* dx, float* dgamma, float* dbeta, double* part, frtm_stream_t stream);
 /* dx = y > 0 ? dy : 0 for n elements (ReLU backward from the saved output; dx may alias dy) */
