@@ -64,6 +64,10 @@ SIGNATURES = {
     'frtm_transpose2d': (I, [P, I, I, P, P]),
     'frtm_conv_pack_weights': (I, [P, I, I, I, I, P, P, P]),
     'frtm_conv2d': (I, [ctypes.POINTER(ConvDesc), P, P, P, P, P, P, P, P, P]),
+    'frtm_conv2d_act': (I, [ctypes.POINTER(ConvDesc), P, P, P, P, P, P, P, P, I, I, I, P]),
+    'frtm_conv_bf16act_launches': (ctypes.c_long, []),
+    'frtm_backbone_set_bf16_act': (I, [P, I]),
+    'frtm_backbone_act_plan': (I, [P, I, I, I, P, I]),
     'frtm_backbone_create': (I, [I, ctypes.POINTER(P)]),
     'frtm_backbone_destroy': (I, [P]),
     'frtm_backbone_num_convs': (I, [P]),

@@ -22,7 +22,7 @@ struct ConvL : TrunkConv {
   bool loaded = false;
   unsigned have() const { unsigned h = 0; for (int l = 0; l <= FRTM_WLAYOUT_BF16X1_3X3_S2; ++l) h |= (image[l] != nullptr) << l; return h; }
 };
-struct BlockL { int conv[3]; int nconv; int ds; };   // conv indices (ds = -1: identity shortcut)
+typedef TrunkBlock BlockL;      // conv indices (ds = -1: identity shortcut)
 
 // A lane is one independent sub-batch of a forward call: its own activation arena, split-K workspace and (for lanes > 0
 // of a multi-lane pass) its own stream.  Frames do not depend on each other, so the lanes' kernels run concurrently and the
@@ -219,19 +219,41 @@ static int pack_missing(frtm_backbone* bb, const TrunkModes& next) {
 }
 
 // A precision switch (TrunkModes::precision and ::bf16x1_3x3): the images first (a failure leaves the modes as they were), then the modes
-static int set_modes(frtm_backbone* bb, int precision, bool bf16x1_3x3) {
+static int set_modes(frtm_backbone* bb, int precision, bool bf16x1_3x3, bool bf16_act) {
   TrunkModes next = bb->modes;
   next.precision = precision;
   next.bf16x1_3x3 = bf16x1_3x3;
+  next.bf16_act = bf16_act;
   int rc = pack_missing(bb, next);
   if (rc) return rc;
-  if (next.precision != bb->modes.precision || next.bf16x1_3x3 != bb->modes.bf16x1_3x3) bb->generation += 1;       // captured graphs hold the other kernels
+  if (next.precision != bb->modes.precision || next.bf16x1_3x3 != bb->modes.bf16x1_3x3 || next.bf16_act != bb->modes.bf16_act) bb->generation += 1;       // captured graphs hold the other kernels
   bb->modes = next;
   return FRTM_OK;
 }
 
+// act_plan (csrc/trunk_route.h) for this handle: `held` = with the images the convs hold now (a pass), else with those their modes want (the
+// device-free query; the same for a loaded conv).  fmt is left EMPTY when the bf16x1_act mode is not in effect: every tensor fp32, nothing to ask.
+static void pass_formats(const frtm_backbone* bb, int B, int H, int W, bool held, std::vector<ActFmt>& fmt) {
+  const TrunkModes& m = bb->modes;
+  const int n = (int)bb->convs.size();
+  if (!(m.bf16_act && m.precision == 2 && m.bf16x1_3x3)) {
+    if (held) fmt.clear();
+    else fmt.assign(n, ActFmt{FRTM_ACT_FP32, FRTM_ACT_FP32, FRTM_ACT_FP32});
+    return;
+  }
+  std::vector<const TrunkConv*> convs(n);
+  std::vector<unsigned> have(n);
+  for (int i = 0; i < n; ++i) { convs[i] = &bb->convs[i]; have[i] = held ? bb->convs[i].have() : wanted_images(m, bb->convs[i]); }
+  const TrunkBlock* stage[4];
+  int nblocks[4];
+  for (int s = 0; s < 4; ++s) { stage[s] = bb->stages[s].data(); nblocks[s] = (int)bb->stages[s].size(); }
+  fmt.resize(n);
+  act_plan(m, convs.data(), have.data(), n, stage, nblocks, B, H, W, fmt.data());
+}
+
+// in / residual / out in the formats `af` names (nullptr: all fp32); a bf16 tensor lies in the first half of its float buffer
 static int run_conv(frtm_backbone* bb, Lane& ln, int idx, int B, int Hin, int Win, const float* in, const float* residual, int relu,
-                    float* out, int* Ho, int* Wo, hipStream_t st, int pad_override = -1) {
+                    float* out, int* Ho, int* Wo, hipStream_t st, int pad_override = -1, const ActFmt* af = nullptr) {
   ConvL& c = bb->convs[idx];
   if (!c.loaded) { frtm_set_error("backbone: conv %d has no weights (call frtm_backbone_set_conv)", idx); return FRTM_ERR_STATE; }
   const int pad = pad_override >= 0 ? pad_override : c.pad;   // (the stem runs on an image whose border the normalisation kernel has written)
@@ -260,6 +282,10 @@ static int run_conv(frtm_backbone* bb, Lane& ln, int idx, int B, int Hin, int Wi
   d.ws_elems = (int)std::min<size_t>(r.ws4_elems ? ln.ws4_elems : ln.ws_elems, 0x7fffffff);
   // workspace: the transformed tensors of the three-launch forms, split-K partials / the fused F(2x2) kernel's scratch, none for the bf16 forms
   float* ws = r.ws4_elems ? ln.ws4 : r.layout >= FRTM_WLAYOUT_BF16X3 ? nullptr : ln.ws;
+  if (af && (af->in || af->res || af->out)) {
+    if (r.layout < FRTM_WLAYOUT_BF16X1) { frtm_set_error("backbone: conv %d has a bf16 operand but takes the fp32 form %d", idx, r.layout); return FRTM_ERR_STATE; }
+    return frtm_conv2d_act(&d, in, c.image[r.layout], nullptr, c.scale, c.shift, residual, out, ws, af->in, residual ? af->res : FRTM_ACT_FP32, af->out, st);
+  }
   return frtm_conv2d(&d, in, c.image[r.layout], r.layout == base_layout(c) ? c.ktab : nullptr, c.scale, c.shift, residual, out, ws, st);
 }
 
@@ -327,6 +353,9 @@ static int forward_lane(frtm_backbone* bb, Lane& ln, const unsigned char* image_
   FRTM_LAUNCH_CHECK();
   int ch = Hp, cw = Wp;
   float* taps[4] = {layer2, layer3, layer4, layer5};
+  std::vector<ActFmt> fmt;                                    // bf16x1_act: the stored format of every block tensor of this pass (else empty)
+  pass_formats(bb, B, H, W, true, fmt);
+  const auto af = [&](int idx) { return fmt.empty() ? nullptr : &fmt[idx]; };
   // scratch rotation: x lives in buf[2] or buf[3] (or a tap); t1,t2,t3 in buf[0],buf[1],buf[4]; buf[5] spare
   for (int s = 0; s < 4 && (s + 2) <= stop_after_layer; ++s) {
     const auto& blocks = bb->stages[s];
@@ -340,7 +369,7 @@ static int forward_lane(frtm_backbone* bb, Lane& ln, const unsigned char* image_
       int ho, wo, h2, w2, hd, wd;
       const float* idn = x;
       if (bl.ds >= 0) {
-        rc = run_conv(bb, ln, bl.ds, B, ch, cw, x, nullptr, 0, t3, &hd, &wd, st);
+        rc = run_conv(bb, ln, bl.ds, B, ch, cw, x, nullptr, 0, t3, &hd, &wd, st, -1, af(bl.ds));
         if (rc) return rc;
         idn = t3;
       }
@@ -349,16 +378,16 @@ static int forward_lane(frtm_backbone* bb, Lane& ln, const unsigned char* image_
         static const int trunk_ablate = getenv("FRTM_TRUNK_ABLATE") ? atoi(getenv("FRTM_TRUNK_ABLATE")) : 0;
         if ((trunk_ablate & 1) && s < 2 && bl.ds < 0) { ho = ch; wo = cw; } else      // conv1 of the identity-shortcut blocks NOT run (results wrong on purpose)
 #endif
-        rc = run_conv(bb, ln, bl.conv[0], B, ch, cw, x, nullptr, 1, t1, &ho, &wo, st);
+        rc = run_conv(bb, ln, bl.conv[0], B, ch, cw, x, nullptr, 1, t1, &ho, &wo, st, -1, af(bl.conv[0]));
         if (rc) return rc;
-        rc = run_conv(bb, ln, bl.conv[1], B, ho, wo, t1, nullptr, 1, t2, &h2, &w2, st);
+        rc = run_conv(bb, ln, bl.conv[1], B, ho, wo, t1, nullptr, 1, t2, &h2, &w2, st, -1, af(bl.conv[1]));
         if (rc) return rc;
-        rc = run_conv(bb, ln, bl.conv[2], B, h2, w2, t2, idn, 1, outp, &ho, &wo, st);
+        rc = run_conv(bb, ln, bl.conv[2], B, h2, w2, t2, idn, 1, outp, &ho, &wo, st, -1, af(bl.conv[2]));
         if (rc) return rc;
       } else {
-        rc = run_conv(bb, ln, bl.conv[0], B, ch, cw, x, nullptr, 1, t1, &h2, &w2, st);
+        rc = run_conv(bb, ln, bl.conv[0], B, ch, cw, x, nullptr, 1, t1, &h2, &w2, st, -1, af(bl.conv[0]));
         if (rc) return rc;
-        rc = run_conv(bb, ln, bl.conv[1], B, h2, w2, t1, idn, 1, outp, &ho, &wo, st);
+        rc = run_conv(bb, ln, bl.conv[1], B, h2, w2, t1, idn, 1, outp, &ho, &wo, st, -1, af(bl.conv[1]));
         if (rc) return rc;
       }
       ch = ho; cw = wo;
@@ -496,19 +525,35 @@ int frtm_backbone_set_winograd(frtm_backbone_t* bb, int enable) {
 int frtm_backbone_set_precision(frtm_backbone_t* bb, int mode) {
   FRTM_CHECK_ARG(bb, "frtm_backbone_set_precision: null handle");
   FRTM_CHECK_ARG(mode == 0 || mode == 1, "frtm_backbone_set_precision: mode must be 0 (fp32) or 1 (bf16x3), got %d", mode);
-  return set_modes(bb, mode, bb->modes.bf16x1_3x3);
+  return set_modes(bb, mode, bb->modes.bf16x1_3x3, bb->modes.bf16_act);
 }
 
 int frtm_backbone_set_bf16_pieces(frtm_backbone_t* bb, int pieces) {
   FRTM_CHECK_ARG(bb, "frtm_backbone_set_bf16_pieces: null handle");
   FRTM_CHECK_ARG(pieces == 0 || pieces == 1 || pieces == 3, "frtm_backbone_set_bf16_pieces: pieces must be 0 (fp32), 1 (bf16x1) or 3 (bf16x3), got %d", pieces);
-  return set_modes(bb, pieces == 3 ? 1 : pieces == 1 ? 2 : 0, bb->modes.bf16x1_3x3);
+  return set_modes(bb, pieces == 3 ? 1 : pieces == 1 ? 2 : 0, bb->modes.bf16x1_3x3, bb->modes.bf16_act);
 }
 
 int frtm_backbone_set_bf16x1_3x3(frtm_backbone_t* bb, int on) {
   FRTM_CHECK_ARG(bb, "frtm_backbone_set_bf16x1_3x3: null handle");
   FRTM_CHECK_ARG(on == 0 || on == 1, "frtm_backbone_set_bf16x1_3x3: on must be 0 or 1, got %d", on);
-  return set_modes(bb, bb->modes.precision, on != 0);
+  return set_modes(bb, bb->modes.precision, on != 0, bb->modes.bf16_act);
+}
+
+int frtm_backbone_set_bf16_act(frtm_backbone_t* bb, int on) {
+  FRTM_CHECK_ARG(bb, "frtm_backbone_set_bf16_act: null handle");
+  FRTM_CHECK_ARG(on == 0 || on == 1, "frtm_backbone_set_bf16_act: on must be 0 or 1, got %d", on);
+  return set_modes(bb, bb->modes.precision, bb->modes.bf16x1_3x3, on != 0);
+}
+
+int frtm_backbone_act_plan(const frtm_backbone_t* bb, int B, int H, int W, int* out3_per_conv, int capacity) {
+  FRTM_CHECK_ARG(bb && out3_per_conv, "frtm_backbone_act_plan: null argument");
+  FRTM_CHECK_ARG(B > 0 && H >= 32 && W >= 32, "frtm_backbone_act_plan: no pass of %d frames of %d x %d", B, H, W);
+  FRTM_CHECK_ARG(capacity >= (int)bb->convs.size(), "frtm_backbone_act_plan: room for %d convs, the trunk has %d", capacity, (int)bb->convs.size());
+  std::vector<ActFmt> fmt;
+  pass_formats(bb, B, H, W, false, fmt);
+  for (size_t i = 0; i < bb->convs.size(); ++i) { out3_per_conv[3 * i] = fmt[i].in; out3_per_conv[3 * i + 1] = fmt[i].res; out3_per_conv[3 * i + 2] = fmt[i].out; }
+  return FRTM_OK;
 }
 
 int frtm_backbone_set_winograd4(frtm_backbone_t* bb, int enable) {

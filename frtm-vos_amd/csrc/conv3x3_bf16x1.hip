@@ -244,3 +244,5 @@ int frtm_bf16x1_3x3_launch(ConvParams p, int tile, hipStream_t st) {
 }
 
 extern "C" long frtm_conv_bf16x1_3x3_launches(void) { return g_bf16x1_3x3_launches.load(); }
+// a launch of this layout's format-aware form (csrc/conv_bf16act.hip) counts here as well
+void frtm_bf16x1_3x3_count_launch() { g_bf16x1_3x3_launches += 1; }

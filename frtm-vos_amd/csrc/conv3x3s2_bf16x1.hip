@@ -222,3 +222,5 @@ int frtm_bf16x1_3x3s2_launch(ConvParams p, int tile, hipStream_t st) {
 }
 
 extern "C" long frtm_conv_bf16x1_3x3s2_launches(void) { return g_bf16x1_3x3s2_launches.load(); }
+// a launch of this layout's format-aware form (csrc/conv_bf16act.hip) counts here as well
+void frtm_bf16x1_3x3s2_count_launch() { g_bf16x1_3x3s2_launches += 1; }

@@ -240,3 +240,5 @@ int frtm_bf16x1_launch(ConvParams p, int tile, hipStream_t st) {
 }
 
 extern "C" long frtm_conv_bf16x1_launches(void) { return g_bf16x1_launches.load(); }
+// a launch of this layout's format-aware form (csrc/conv_bf16act.hip) counts here as well
+void frtm_bf16x1_count_launch() { g_bf16x1_launches += 1; }

@@ -21,6 +21,7 @@ struct TrunkModes {
   // FRTM_BF16X1_MIN_COLS=n (tests and measurements on small frames): a bf16x1 trunk routes EVERY eligible conv from n columns per launch on, instead of the measured table
   int bf16x1_min_cols = -1;
   bool bf16x1_3x3 = false;     // frtm_backbone_set_bf16x1_3x3: with precision == 2, the routed 3x3 convs on bf16 MFMAs as well; stored whatever the precision is
+  bool bf16_act = false;       // frtm_backbone_set_bf16_act: with precision == 2 && bf16x1_3x3, bf16 storage of the tensors only bf16 kernels touch (act_plan); stored whatever the others are
 };
 
 // The convs a reduced-precision trunk sends to a bf16 kernel, per layout: FRTM_WLAYOUT_BF16X3 (csrc/conv_bf16x3.hip) and _BF16X1 (csrc/conv_bf16x1.hip)
@@ -170,4 +171,66 @@ static inline Route choose_route(const TrunkModes& m, const TrunkConv& c, int B,
   r.tile = c.plan_tile ? c.plan_tile : scanned_tile(c, B, Ho, Wo, false);
   r.splitk = c.plan_splitk;
   return r;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------------------
+// The bf16x1_act mode: the stored format of every tensor of the block walk (csrc/backbone.hip: forward_lane), FRTM_ACT_FP32 or FRTM_ACT_BF16.
+// ---------------------------------------------------------------------------------------------------------------------------------------------
+struct TrunkBlock { int conv[3]; int nconv; int ds; };   // conv indices of a residual block (ds = -1: identity shortcut)
+struct ActFmt { int in, res, out; };                     // FRTM_ACT_* of one conv's input, residual and output
+
+// fmt[i] for each of the n convs of a trunk (convs[i], `have[i]` = the images it holds: choose_route's argument) in one pass of B frames per lane at
+// H x W.  A tensor is bf16 exactly when the mode is in effect (bf16_act with precision == 2 && bf16x1_3x3), its channel count is a multiple of 8,
+// its producer is routed to layout 6, 7 or 8 at that launch and so is every conv that reads it, as input or as residual.  That can hold for a
+// block's t1 (conv1 -> conv2) and t2 (conv2 -> conv3), for a downsample output (-> the last conv's residual) and for a block output that does not
+// end a stage (-> the next block's conv1, its downsample if it has one, else its last conv's residual).  The pool output and every stage output --
+// every tap, wanted or not -- stay fp32, and so does whatever an fp32 form reads or writes.
+static inline void act_plan(const TrunkModes& m, const TrunkConv* const* convs, const unsigned* have, int n, const TrunkBlock* const stage[4],
+                            const int nblocks[4], int B, int H, int W, ActFmt* fmt) {
+  for (int i = 0; i < n; ++i) fmt[i] = {FRTM_ACT_FP32, FRTM_ACT_FP32, FRTM_ACT_FP32};
+  if (!(m.bf16_act && m.precision == 2 && m.bf16x1_3x3)) return;
+  int ch = conv_out_dim(*convs[0], H, convs[0]->pad), cw = conv_out_dim(*convs[0], W, convs[0]->pad);      // the stem, then the 3x3 stride-2 pad-1 pool
+  ch = (ch + 2 - 3) / 2 + 1; cw = (cw + 2 - 3) / 2 + 1;
+  // is conv idx on h x w inputs a bf16x1 launch?  (h, w become its output size)
+  const auto routed = [&](int idx, int& h, int& w) {
+    const TrunkConv& c = *convs[idx];
+    h = conv_out_dim(c, h, c.pad); w = conv_out_dim(c, w, c.pad);
+    const int l = choose_route(m, c, B, h, w, c.pad, have[idx]).layout;
+    return l == FRTM_WLAYOUT_BF16X1 || l == FRTM_WLAYOUT_BF16X1_3X3 || l == FRTM_WLAYOUT_BF16X1_3X3_S2;
+  };
+  for (int s = 0; s < 4; ++s) {
+    bool x_bf16 = false;                        // the block's input: a stage begins on the pool output or a stage output
+    // routed flags of block b's convs (r[0 .. nconv - 1], r[3] = its downsample), worked out one block ahead: a block output asks its readers
+    bool r[4] = {}, rn[4] = {};
+    const auto block_routes = [&](const TrunkBlock& bl, bool* out, int& h, int& w) {
+      int hd = h, wd = w;
+      out[3] = bl.ds >= 0 && routed(bl.ds, hd, wd);
+      for (int k = 0; k < bl.nconv; ++k) out[k] = routed(bl.conv[k], h, w);
+    };
+    if (nblocks[s] > 0) block_routes(stage[s][0], r, ch, cw);
+    for (int b = 0; b < nblocks[s]; ++b) {
+      const TrunkBlock& bl = stage[s][b];
+      const int last = bl.conv[bl.nconv - 1];
+      const bool ends_stage = b + 1 == nblocks[s];
+      if (!ends_stage) block_routes(stage[s][b + 1], rn, ch, cw);
+      fmt[bl.conv[0]].in = x_bf16;
+      for (int k = 0; k + 1 < bl.nconv; ++k) {                      // t1, t2
+        const bool bf = r[k] && r[k + 1] && convs[bl.conv[k]]->Cout % 8 == 0;
+        fmt[bl.conv[k]].out = fmt[bl.conv[k + 1]].in = bf;
+      }
+      if (bl.ds >= 0) {
+        const bool bf = r[3] && r[bl.nconv - 1] && convs[bl.ds]->Cout % 8 == 0;
+        fmt[bl.ds].in = x_bf16;
+        fmt[bl.ds].out = fmt[last].res = bf;
+      } else fmt[last].res = x_bf16;
+      bool out_bf16 = false;
+      if (!ends_stage) {
+        const TrunkBlock& nx = stage[s][b + 1];
+        out_bf16 = r[bl.nconv - 1] && rn[0] && (nx.ds >= 0 ? rn[3] : rn[nx.nconv - 1]) && convs[last]->Cout % 8 == 0;
+      }
+      fmt[last].out = out_bf16;
+      x_bf16 = out_bf16;
+      for (int k = 0; k < 4; ++k) r[k] = rn[k];
+    }
+  }
 }

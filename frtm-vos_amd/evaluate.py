@@ -27,8 +27,8 @@ class Parameters:
         # (h, w): frames of any other size are resized to it on the device and tracked there; label maps and masks come back at the frames'
         # native size (Tracker(working_size=...)).  None: frames are tracked at the size they arrive in
         self.working_size = None if working_size is None else (int(working_size[0]), int(working_size[1]))
-        if trunk_precision not in ('fp32', 'bf16x3', 'bf16x1', 'bf16x1_3x3'):
-            raise ValueError("trunk_precision must be 'fp32', 'bf16x3', 'bf16x1' or 'bf16x1_3x3', got %r" % (trunk_precision,))
+        if trunk_precision not in ('fp32', 'bf16x3', 'bf16x1', 'bf16x1_3x3', 'bf16x1_act'):
+            raise ValueError("trunk_precision must be 'fp32', 'bf16x3', 'bf16x1', 'bf16x1_3x3' or 'bf16x1_act', got %r" % (trunk_precision,))
         self.trunk_precision = trunk_precision    # 'fp32', 'bf16x3', 'bf16x1': the trunk's routed stride-1 1x1 convs on bf16 pieces; 'bf16x1_3x3': its routed 3x3 convs too (ResnetFeatureExtractor.precision)
         if refiner_precision not in ('fp32', 'bf16x1'):
             raise ValueError("refiner_precision must be 'fp32' or 'bf16x1', got %r" % (refiner_precision,))
@@ -146,11 +146,12 @@ def parse_args(argv=None):
                     help="refiner head: 'compat' (BackwardCompatibleUpsampler, the reference's default) or 'bicubic' (Upsampler, the fork's head)")
     ap.add_argument('--ytvos-fork', action='store_true',
                     help="a checkpoint of the reference's YouTube-VOS fork: shorthand for --ytvos-solver --ytvos-merge --upsampler bicubic")
-    ap.add_argument('--trunk-precision', choices=['fp32', 'bf16x3', 'bf16x1', 'bf16x1_3x3'], default='fp32',
+    ap.add_argument('--trunk-precision', choices=['fp32', 'bf16x3', 'bf16x1', 'bf16x1_3x3', 'bf16x1_act'], default='fp32',
                     help="'bf16x3': the routed stride-1 1x1 trunk convs on three bf16 pieces per operand (not bitwise fp32: 0.78-1.40x the fp32 kernels' max error against fp64; "
                          "no measurable speed-up of the trunk or the tracker); 'bf16x1': on one bf16 piece per operand, fp32 accumulation (NOT fp32-level arithmetic: "
                          "up to 2^-7 relative error per product); 'bf16x1_3x3': bf16x1 with the routed 3x3 convs of stride 1 and 2 on one bf16 piece as well (the "
-                         "only bf16 mode that reaches ResNet-18); README, DESIGN.md section 4")
+                         "only bf16 mode that reaches ResNet-18); 'bf16x1_act': bf16x1_3x3 with the block-internal activations that only routed convs touch stored as "
+                         "bf16 (fp32 taps); README, DESIGN.md section 4")
     ap.add_argument('--refiner-precision', choices=['fp32', 'bf16x1'], default='fp32',
                     help="'bf16x1': the refiner's routed 3x3 convs on one bf16 piece per operand, fp32 accumulation (NOT fp32-level arithmetic: up to 2^-7 "
                          "relative error per product; the 1x1 convs and the glue stay fp32); README, DESIGN.md section 4")

@@ -115,8 +115,9 @@ class ResNetParams(nn.Module):
         return self
 
 
-# bf16 pieces per operand (frtm_backbone_set_bf16_pieces); 'bf16x1_3x3' is bf16x1 with the routed 3x3 convs on bf16 MFMAs as well (frtm_backbone_set_bf16x1_3x3)
-_PRECISIONS = {'fp32': 0, 'bf16x3': 3, 'bf16x1': 1, 'bf16x1_3x3': 1}
+# bf16 pieces per operand (frtm_backbone_set_bf16_pieces); 'bf16x1_3x3' is bf16x1 with the routed 3x3 convs on bf16 MFMAs as well (frtm_backbone_set_bf16x1_3x3);
+# 'bf16x1_act' is bf16x1_3x3 with bf16 storage of the activations that only bf16 kernels touch (frtm_backbone_set_bf16_act)
+_PRECISIONS = {'fp32': 0, 'bf16x3': 3, 'bf16x1': 1, 'bf16x1_3x3': 1, 'bf16x1_act': 1}
 
 
 class ResnetFeatureExtractor:
@@ -165,6 +166,7 @@ class ResnetFeatureExtractor:
         self._winograd4 = not os.environ.get('FRTM_NO_WINO4')
         self._winograd6 = not os.environ.get('FRTM_NO_WINO6')
         self._precision = precision
+        self._act_storage = False      # what the handle's frtm_backbone_set_bf16_act switch holds (a new handle: off)
         self.use_graph = False         # with reuse_outputs: replay a captured hipGraph per (batch, size) instead of enqueuing the launches
         self.capture_after = 1         # trunk shapes are replayed as hipGraphs from their (capture_after + 1)-th use on
         self._pass_done = {}           # lane set -> event behind its last pass: a lane set (arenas, scratch) runs one pass at a time
@@ -202,12 +204,20 @@ class ResnetFeatureExtractor:
         on one (operands rounded to bf16, fp32 accumulation: NOT fp32-level arithmetic) (frtm_backbone_set_bf16_pieces; the error bounds and the
         routed shapes: DESIGN.md sections 4 and 9).  Every other conv stays fp32.  'bf16x1_3x3': bf16x1, and the routed 3x3 pad-1 convs of stride 1
         and 2 on one bf16 piece per operand as well (frtm_backbone_set_bf16x1_3x3) -- the only reduced-precision mode that reaches the BasicBlock
-        trunks (ResNet-18 / 34 have no stride-1 1x1 conv)."""
+        trunks (ResNet-18 / 34 have no stride-1 1x1 conv).  'bf16x1_act': bf16x1_3x3, and every block-internal tensor that only routed convs write
+        and read is STORED as bf16 (frtm_backbone_set_bf16_act; include/frtm_hip.h: FRTM_ACT_BF16).  The taps stay fp32; against bf16x1_3x3 the only
+        new rounding is the value a residual operand carries."""
         return self._precision
 
     def _apply_precision(self, mode):
         H.call_nostream('frtm_backbone_set_bf16_pieces', self._handle, _PRECISIONS[mode])
-        H.call_nostream('frtm_backbone_set_bf16x1_3x3', self._handle, int(mode == 'bf16x1_3x3'))
+        H.call_nostream('frtm_backbone_set_bf16x1_3x3', self._handle, int(mode in ('bf16x1_3x3', 'bf16x1_act')))
+        # frtm_backbone_set_bf16_act is idempotent, so calling it every time would compute the same thing.  _act_storage shadows the handle's switch
+        # only so that the call is made when the switch has to move: the other modes then make exactly the library calls they made before this mode
+        # existed (tests of those modes pin the list of calls), and they keep working against a library built without the entry point.
+        if (mode == 'bf16x1_act') != self._act_storage:
+            H.call_nostream('frtm_backbone_set_bf16_act', self._handle, int(mode == 'bf16x1_act'))
+            self._act_storage = mode == 'bf16x1_act'
 
     @precision.setter
     def precision(self, mode):

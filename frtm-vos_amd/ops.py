@@ -92,15 +92,44 @@ def wino4_workspace(B, Cin, Cout, Hh, Ww, device, m=4):
     return torch.empty((m + 2) ** 2 * (Cin + Cout) * tiles, device=device)
 
 
+def act_to_bf16(x):
+    """(B,C,H,W) float tensor -> the bf16 activation layout FRTM_ACT_BF16 of include/frtm_hip.h as a flat bfloat16 tensor: element (img, c, p) at
+    index ((img * C/8 + c/8) * H*W + p) * 8 + c%8, rounded to nearest even.  Plain torch ops, for tests and tools: the trunk converts nowhere."""
+    B, C, Hh, Ww = x.shape
+    if C % 8:
+        raise ValueError('act_to_bf16: the bf16 activation layout needs C %% 8 == 0 (got %d)' % C)
+    return x.to(torch.bfloat16).reshape(B, C // 8, 8, Hh * Ww).permute(0, 1, 3, 2).contiguous().reshape(-1)
+
+
+def act_from_bf16(buf, shape):
+    """The inverse of act_to_bf16: a flat bfloat16 buffer in the FRTM_ACT_BF16 layout of a ``shape`` = (B,C,H,W) tensor -> float32 NCHW (exact)."""
+    B, C, Hh, Ww = shape
+    if C % 8 or buf.dtype != torch.bfloat16 or buf.numel() != B * C * Hh * Ww:
+        raise ValueError('act_from_bf16: needs C %% 8 == 0 and a bfloat16 buffer of B*C*H*W elements')
+    return buf.reshape(B, C // 8, Hh * Ww, 8).permute(0, 1, 3, 2).reshape(B, C, Hh, Ww).float().contiguous()
+
+
 def conv2d(x, wT, Cout, ksize=1, stride=1, pad=0, ktab=None, scale=None, shift=None, residual=None, relu=False,
-           out=None, out_transposed=False, splitk=0, tile=0, shape=None, w_pitch=0, w_layout=0, ws=None):
+           out=None, out_transposed=False, splitk=0, tile=0, shape=None, w_pitch=0, w_layout=0, ws=None, in_fmt=0, res_fmt=0, out_fmt=0):
     """fp32 MFMA implicit-GEMM convolution.  x: (B,Cin,H,W) dense (or any dense buffer when ``shape``
     = (B,Cin,H,W) is given explicitly); wT: packed weights from pack_weights(), or a plain [K, w_pitch]
     matrix when w_pitch > 0.  Returns (B,Cout,Ho,Wo) (or (B,Ho*Wo,Cout)
-    when out_transposed)."""
+    when out_transposed).
+    ``in_fmt`` / ``res_fmt`` / ``out_fmt`` = 1 (FRTM_ACT_BF16; bf16x1 layouts 6, 7, 8 only, frtm_conv2d_act): x / residual is a flat bfloat16 buffer
+    from act_to_bf16 (``shape`` is then required) / the result is one (read it with act_from_bf16)."""
     B, Cin, Hin, Win = shape if shape is not None else x.shape
     Ho = (Hin + 2 * pad - ksize) // stride + 1
     Wo = (Win + 2 * pad - ksize) // stride + 1
+    if in_fmt or res_fmt or out_fmt:
+        for name, t, fmt in (('x', x, in_fmt), ('residual', residual, res_fmt), ('out', out, out_fmt)):
+            if t is not None and t.dtype != (torch.bfloat16 if fmt else torch.float32):
+                raise TypeError('conv2d: %s must be %s under format %d' % (name, 'bfloat16' if fmt else 'float32', fmt))
+        if out is None:
+            out = torch.empty(B * Cout * Ho * Wo, device=x.device, dtype=torch.bfloat16) if out_fmt else torch.empty((B, Cout, Ho, Wo), device=x.device)
+        d = H.ConvDesc(B, Cin, Hin, Win, Cout, ksize, stride, pad, int(relu), int(out_transposed), int(splitk), int(tile), int(w_layout), 0, int(w_pitch))
+        H.call('frtm_conv2d_act', ctypes.byref(d), H.ptr(x), H.ptr(wT), H.ptr(ktab), H.ptr(scale), H.ptr(shift), H.ptr(residual), H.ptr(out), None,
+               int(in_fmt), int(res_fmt), int(out_fmt))
+        return out
     if out is None:
         out = torch.empty((B, Ho * Wo, Cout) if out_transposed else (B, Cout, Ho, Wo), device=x.device, dtype=torch.float32)
     if w_pitch > 0 and (w_pitch % 4 or wT.data_ptr() % 16):

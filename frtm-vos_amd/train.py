@@ -30,8 +30,8 @@ class ModelParameters:
                  refiner_precision='fp32', batched_scores=False):
         self.name, self.device, self.batch_size = name, device, batch_size
         self.batched_scores = bool(batched_scores)    # the batch's target models score their frames in one grouped launch (TrainerModel.batched_scores)
-        if trunk_precision not in ('fp32', 'bf16x3', 'bf16x1', 'bf16x1_3x3'):
-            raise ValueError("trunk_precision must be 'fp32', 'bf16x3', 'bf16x1' or 'bf16x1_3x3', got %r" % (trunk_precision,))
+        if trunk_precision not in ('fp32', 'bf16x3', 'bf16x1', 'bf16x1_3x3', 'bf16x1_act'):
+            raise ValueError("trunk_precision must be 'fp32', 'bf16x3', 'bf16x1', 'bf16x1_3x3' or 'bf16x1_act', got %r" % (trunk_precision,))
         self.trunk_precision = trunk_precision        # the frozen trunk's routed 1x1 convs on bf16 pieces (ResnetFeatureExtractor.precision)
         if refiner_precision not in ('fp32', 'bf16x1'):
             raise ValueError("refiner_precision must be 'fp32' or 'bf16x1', got %r" % (refiner_precision,))
@@ -88,9 +88,9 @@ def parse_args(argv=None):
     ap.add_argument('--workspace', default='workspace', help='checkpoints/, logs/ and tmodels_cache/ are created below it')
     ap.add_argument('--synthetic-sequences', type=int, default=32)
     ap.add_argument('--synthetic-size', default='480x854', help='HxW of the synthetic frames')
-    ap.add_argument('--trunk-precision', choices=['fp32', 'bf16x3', 'bf16x1', 'bf16x1_3x3'], default='fp32',
+    ap.add_argument('--trunk-precision', choices=['fp32', 'bf16x3', 'bf16x1', 'bf16x1_3x3', 'bf16x1_act'], default='fp32',
                     help="the frozen trunk's routed 1x1 convs: fp32, three bf16 pieces (fp32-level) or one bf16 piece (NOT fp32-level); "
-                         "bf16x1_3x3: one bf16 piece for the routed 3x3 convs as well")
+                         "bf16x1_3x3: one bf16 piece for the routed 3x3 convs as well; bf16x1_act: that, with bf16 storage of the activations between routed convs")
     ap.add_argument('--refiner-precision', choices=['fp32', 'bf16x1'], default='fp32',
                     help="the refiner's training pass: bf16x1 runs the routed 3x3 convs, input and weight gradients on bf16 MFMAs with fp32 "
                          "accumulation (NOT fp32-level; master weights, BatchNorm, 1x1 convs and checkpoints stay fp32)")

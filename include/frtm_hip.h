@@ -349,6 +349,23 @@ int frtm_conv_pack_weights(const float* w_oihw, int Cout, int Cin, int ksize, in
 int frtm_conv2d(const frtm_conv_desc* desc_host, const float* in, const float* wT, const int* ktab,
                 const float* scale, const float* shift, const float* residual, float* out,
                 float* workspace, frtm_stream_t stream);
+/* Activation formats of frtm_conv2d_act (the opt-in bf16x1_act trunk mode, csrc/conv_bf16act.hip).
+   FRTM_ACT_FP32 (0): dense NCHW fp32, what every other entry point reads and writes.
+   FRTM_ACT_BF16 (1): bf16, channel-blocked by 8; needs C % 8 == 0 and a 16-byte aligned base.  Element (img, c, p) of a (B, C, H, W) tensor lies at
+   bf16 index ((img * C/8 + c/8) * H*W + p) * 8 + c%8: every 8-channel slice of a pixel is 16 contiguous, 16-byte aligned bytes -- the [k/8][n][8]
+   slot form in which the three bf16x1 kernels stage activations in LDS.  B*C*H*W*2 bytes.  Values are rounded on store to nearest even, the
+   conversion the bf16x1 kernels apply to an fp32 input on load; NaN stays NaN and Inf stays Inf. */
+#define FRTM_ACT_FP32 0
+#define FRTM_ACT_BF16 1
+/* frtm_conv2d with the input, the residual and the output each in its own format (in / residual / out point at fp32 or bf16 data accordingly; the
+   residual's format is ignored when residual is NULL).  All three FRTM_ACT_FP32: frtm_conv2d itself.  Otherwise w_layout must be FRTM_WLAYOUT_BF16X1,
+   _BF16X1_3X3 or _BF16X1_3X3_S2 with that layout's geometry, tile values and image; no out_transposed, no split-K, no w_pitch; Cin % 8 == 0 for a bf16
+   input, Cout % 8 == 0 for a bf16 residual or output; bf16 tensors 16-byte aligned.  Anything else is FRTM_ERR_ARG and launches nothing.  The result is
+   a bit-exact function of the fp32-format result of the same layout: a bf16 input changes nothing (the kernel rounds an fp32 input to bf16 anyway), a
+   bf16 residual acts as its fp32 widening, a bf16 output is the fp32 output rounded to nearest even.  Workspace and ktab are not used by these forms. */
+int frtm_conv2d_act(const frtm_conv_desc* desc_host, const void* in, const float* wT, const int* ktab,
+                    const float* scale, const float* shift, const void* residual, void* out,
+                    float* workspace, int in_fmt, int res_fmt, int out_fmt, frtm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Backbone: torchvision-topology ResNet trunk (model/feature_extractor.py:9-68), weights resident.
@@ -416,6 +433,9 @@ long frtm_conv_bf16x1_launches(void);
 long frtm_conv_bf16x1_3x3_launches(void);
 /* ... and that took the bf16x1 3x3 stride-2 form (FRTM_WLAYOUT_BF16X1_3X3_S2, csrc/conv3x3s2_bf16x1.hip): its own counter again, the layout-7 one does not move. */
 long frtm_conv_bf16x1_3x3s2_launches(void);
+/* Launches of frtm_conv2d_act (this process) with at least one bf16 operand (csrc/conv_bf16act.hip).  Such a launch ALSO counts in the counter of its
+ * layout above; an all-fp32 frtm_conv2d_act call is a frtm_conv2d call and does not count here. */
+long frtm_conv_bf16act_launches(void);
 /* Host-side check of the multiplication the conv kernels use instead of integer divisions in their index arithmetic (csrc/conv_common.h: FastDiv,
  * q = (mulhi(n, m) + n) >> s with m, s prepared per divisor): returns n / d as that formula computes it, for 0 <= n < 2^31, d >= 1.
  * No GPU involved; tests/test_cpu_host.py sweeps it against Python's integer division. */
@@ -462,6 +482,20 @@ int frtm_backbone_set_bf16_pieces(frtm_backbone_t* bb, int pieces);
  * stem and the 1x1 convs are handled as without the flag.  Images are packed when the flag first turns on (and again by a later
  * frtm_backbone_set_conv): for every 3x3 conv of ResNet-101 about 43 MB of device memory.  Bumps the generation when the flag's value changes. */
 int frtm_backbone_set_bf16x1_3x3(frtm_backbone_t* bb, int on);
+/* bf16 storage of the activations that only bf16 kernels touch (the bf16x1_act trunk mode): on = 1 / 0; anything else is FRTM_ERR_ARG and leaves the
+ * state as it was.  Stored whatever the other switches are; takes effect only while the pieces mode is 1 AND the 3x3 flag is on.  Then a tensor of
+ * the block walk (a block's t1 / t2, a downsample output, a block output that does not end a stage) is held as FRTM_ACT_BF16 exactly when its
+ * channel count is a multiple of 8, the conv that writes it is routed to layout 6, 7 or 8 at that launch, and so is EVERY conv that reads it, as
+ * input or as residual (csrc/trunk_route.h: act_plan).  The normalised image, the stem and pool outputs, every stage output (every tap, wanted or
+ * not) and anything an fp32 form touches stay fp32, so the fp32 kernels never meet a bf16 tensor and the taps stay dense NCHW fp32.  Against
+ * bf16x1_3x3 the only new rounding is the value a residual operand carries.  Needs no new weight image; the arenas are unchanged (a bf16 tensor
+ * uses half of its buffer).  Bumps the generation when the flag's value changes. */
+int frtm_backbone_set_bf16_act(frtm_backbone_t* bb, int on);
+/* The formats of one pass of B frames per lane at H x W with the handle's modes as they are now: out3_per_conv[3 * i .. 3 * i + 2] = the
+ * {input, residual, output} FRTM_ACT_* of conv #i (forward order, as frtm_backbone_conv_info).  `capacity`: convs the buffer holds, at least
+ * frtm_backbone_num_convs.  All zero unless the bf16x1_act mode is in effect.  The decision of the forward pass itself; needs neither weights nor a
+ * device. */
+int frtm_backbone_act_plan(const frtm_backbone_t* bb, int B, int H, int W, int* out3_per_conv, int capacity);
 
 /* ------------------------------------------------------------------------------------------
  * Tracker.track mask merge (model/tracker.py:214-221), in place on masks (n_obj+1, H*W).
