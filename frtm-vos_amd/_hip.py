@@ -163,6 +163,7 @@ SIGNATURES = {
     'frtm_masks_to_native': (I, [P, ctypes.c_size_t, I, I, P, P, I, P, ctypes.c_size_t, P, ctypes.c_size_t, P, ctypes.c_size_t, P]),
     'frtm_resize_label_map_u8': (I, [P, ctypes.c_size_t, P, P, I, P, I, I, P]),
     'frtm_frames_to_rgb_u8': (I, [P, ctypes.c_size_t, P, P, I, P, I, I, P]),
+    'frtm_render_frames_u8': (I, [P, P, I, P]),
 }
 
 _lib = None

@@ -112,13 +112,13 @@ __global__ __launch_bounds__(256) void k_masks_to_native(const float* __restrict
     for (int i = 0; i < 4; ++i) {
       // bilinear_at: the map itself when the sizes agree, else its expression
       const float m = same ? v00[i] : ly0[i] * (lx0 * v00[i] + lx1 * v01[i]) + ly1[i] * (lx0 * v10[i] + lx1 * v11[i]);
-      if (m > best[i]) { best[i] = m; arg[i] = k; }
+      merged_offer(m, k, best[i], arg[i]);
       if (sdst && col_ok && tg + 4 * i < th) sdst[((size_t)k * H + (y0 + tg + 4 * i)) * W + xo] = m;
     }
   }
 #pragma unroll
   for (int i = 0; i < 4; ++i)
-    if (col_ok && tg + 4 * i < th) lab[(size_t)(y0 + tg + 4 * i) * W + xo] = lut[(arg[i] >= 1 && best[i] > 0.5f) ? arg[i] : 0];
+    if (col_ok && tg + 4 * i < th) lab[(size_t)(y0 + tg + 4 * i) * W + xo] = lut[merged_plane(arg[i], best[i])];
 }
 
 // k_resize_labels of frame_resize.hip with the id copied instead of compared: the same source index, the same float32 product.

@@ -15,6 +15,14 @@ constexpr int INJ_CG = 4;      // channel groups per object (more workgroups on 
 constexpr int CAB_RB = 16;     // rows of one plane per block: 64 x 4 threads, every thread 4 rows of its columns
 constexpr int MERGE_MAX = 16;  // planes of one frame (background + 15 objects) that the merge and the way back to the native size hold per thread
 
+// ---- the label of one pixel of a MERGED mask stack (every plane but the winner is 0), defined once for the way back to the native size
+// (native_size.hip) and the renderer (frame_render.hip):
+//   arg = the first k with the largest m_k (planes offered in order 0, 1, ...; a NaN never wins), plane = arg if arg >= 1 and m_arg > 0.5f, else 0
+__device__ __forceinline__ void merged_offer(float m, int k, float& best, int& arg) {
+  if (m > best) { best = m; arg = k; }
+}
+__device__ __forceinline__ int merged_plane(int arg, float best) { return (arg >= 1 && best > 0.5f) ? arg : 0; }
+
 // ---- which frame does sample n belong to?  (passed by value; false: the sample is skipped, before any barrier) ----
 struct FrameByGroup {          // `group` consecutive samples (the objects of one frame) share a frame
   int group;

@@ -139,6 +139,7 @@ class StreamPool:
         self.refiner_passes = 0         # refiner calls made by groups so far (diagnostics)
         self.trunk_passes = 0           # trunk calls made by step() so far (diagnostics)
         self.frame_launches = 0         # ops.FramePlan launches made by step() so far: one per TickBatch that holds a DecoderFrame (diagnostics)
+        self.render_launches = 0        # ops.render_frames launches made by render() so far: one per call (diagnostics)
         self._frame_plans = {}          # layouts of a tick's batch, in order -> (ops.FramePlan, staging buffer, byte offsets and counts)
         self._plans = {}                # native sizes of a tick's batch, in order -> (ops.ResizePlan, staging buffer, byte offsets)
         self._native = {}               # (group key, native sizes) -> [ops.NativeTable, labels, soft, object ids of the rows, their LUTs]
@@ -249,6 +250,28 @@ class StreamPool:
         for sid in frames:
             self._streams[sid].tracker.current_frame += 1
         return out
+
+    @torch.no_grad()
+    def render(self, frames, style=None, out=None):
+        """The last answer of every stream named drawn onto its frame: {sid: image (3,H,W) uint8 or ops.DecoderFrame} -> {sid: rendered
+        frame}, ONE ops.render_frames launch for all of them whatever their sizes and formats.  A stream whose last step went the way
+        back from the working size is drawn from ``native_labels[sid]``, every other one from its ``current_masks`` and object LUT;
+        ValueError when that answer has another size than the frame.  ``style``: an ops.RenderStyle (default: the DAVIS palette at half
+        opacity); ``out``: None (new frames of the same kind and layout), ``frames`` itself (in place) or {sid: the caller's surface}."""
+        sids = list(frames)
+        if not sids:
+            return {}
+        if out is not None and sorted(out, key=repr) != sorted(sids, key=repr):
+            raise KeyError('StreamPool.render: out names other streams than frames')
+        answers, luts = [], []
+        for sid in sids:
+            answer, lut = self._streams[sid].tracker.render_answer(frames[sid], self.native_labels.get(sid))
+            answers.append(answer)
+            luts.append(lut)
+        done = ops.render_frames([frames[sid] for sid in sids], answers, ops.default_render_style() if style is None else style, luts=luts,
+                                 out=None if out is None else [out[sid] for sid in sids])
+        self.render_launches += 1
+        return dict(zip(sids, done))
 
     def _resize_batch(self, tb, natives, frames, batch):
         """The tick's frames, of any sizes, into ``batch`` (B,3,h,w) at the working size: copied into ONE packed staging buffer (16-byte

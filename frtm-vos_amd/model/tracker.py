@@ -1118,6 +1118,29 @@ class Tracker(nn.Module):
             image = self._decode(image) if features is None else None
         return self._track(image, features, size)
 
+    def render_answer(self, image, labels):
+        """(answer, lut or None) of ops.render_frames for ``image``: ``labels``, the last step's native label map (``native_labels``; a
+        pool's entry for the stream), when that step went the way back from the working size -- else (None) ``current_masks`` with the
+        object LUT; ValueError when that answer has another size than the frame."""
+        size = tuple(image.shape[-2:])
+        if labels is not None and tuple(labels.shape[-2:]) == size:
+            return labels.reshape(size), None
+        masks = self.current_masks
+        if labels is None and masks is not None and tuple(masks.shape[-2:]) == size and masks.shape[0] == len(self.targets) + 1:
+            return masks.contiguous(), self._object_lut()
+        raise ValueError('render: no answer for a frame of size %r (the last step answered at %s)'
+                         % (size, 'no size: nothing was tracked' if masks is None and labels is None else
+                            tuple((labels if labels is not None else masks).shape[-2:])))
+
+    @torch.no_grad()
+    def render(self, image, style=None, out=None):
+        """The last answer of track() drawn onto its frame ``image`` (a (3, H, W) uint8 tensor or an ops.DecoderFrame) in one launch
+        (ops.render_frames): ``style`` an ops.RenderStyle (default: the DAVIS palette at half opacity), ``out`` None (a new frame of the
+        same kind and layout), ``image`` itself (in place) or the caller's surface.  -> the rendered frame."""
+        answer, lut = self.render_answer(image, self.native_labels)
+        return ops.render_frames([image], [answer], ops.default_render_style() if style is None else style, luts=[lut],
+                                 out=None if out is None else [out])[0]
+
     def _track(self, image, features, im_size):
         if self._unchecked_fits and not self._in_run_sequence:
             self._check_first_frame_fits()

@@ -1,7 +1,9 @@
 """Thin tensor-level wrappers over the C ABI (include/frtm_hip.h).  Every function enqueues HIP
 kernels on the current torch stream and returns torch tensors that own the device memory."""
+import collections
 import ctypes
 import functools
+import numbers
 
 import torch
 
@@ -1041,3 +1043,208 @@ def masks_to_native(masks, table, labels, luts, soft=None, size=None):
     H.call('frtm_masks_to_native', H.ptr(masks), masks.numel(), int(h), int(w), table.rows.data_ptr(), H.ptr(table.dev), table.n,
            H.ptr(labels), labels.numel(), H.ptr(soft), 0 if soft is None else soft.numel(), H.ptr(luts), luts.numel())
     return labels, soft
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# The way out: tracked objects rendered onto RGB and NV12 frames in one launch (csrc/frame_render.hip)
+# ----------------------------------------------------------------------------------------------------------------------
+RENDER_FORMATS = {'rgb': 0, 'nv12': 1}              # FRTM_RENDER_RGB / FRTM_RENDER_NV12
+RENDER_ANSWERS = {'labels': 0, 'masks': 1}          # FRTM_RENDER_LABELS / FRTM_RENDER_MASKS
+RENDER_ROW_WORDS = 20                               # FRTM_RENDER_ROW_WORDS
+# FRAME_FORMATS id of an NV12 format -> (y0, yr, yg, yb, ur, ug, ub, vr, vg, vb): the forward table of include/frtm_hip.h
+RENDER_YUV = {
+    1: (16, 16829, 33039, 6416, -9714, -19071, 28784, 28784, -24103, -4681),
+    2: (0, 19595, 38470, 7471, -11058, -21710, 32768, 32768, -27439, -5329),
+    3: (16, 11966, 40254, 4064, -6596, -22189, 28784, 28784, -26145, -2639),
+    4: (0, 13933, 46871, 4732, -7509, -25259, 32768, 32768, -29763, -3005),
+}
+
+
+def rgb_to_yuv_u8(rgb, fmt):
+    """(..., 3) integer RGB in 0..255 (a CPU tensor) -> (..., 3) uint8 (Y, U, V) by the forward fixed-point formula of include/frtm_hip.h
+    for FRAME_FORMATS id ``fmt`` (1 .. 4): Y = clamp(y0 + ((yr R + yg G + yb B + 32768) >> 16)), U and V around 128 likewise."""
+    y0, yr, yg, yb, ur, ug, ub, vr, vg, vb = RENDER_YUV[int(fmt)]
+    c = rgb.to(torch.int64)
+    r, g, b = c[..., 0], c[..., 1], c[..., 2]
+    yuv = torch.stack([y0 + ((yr * r + yg * g + yb * b + 32768) >> 16), 128 + ((ur * r + ug * g + ub * b + 32768) >> 16),
+                       128 + ((vr * r + vg * g + vb * b + 32768) >> 16)], dim=-1)
+    return yuv.clamp_(0, 255).to(torch.uint8)
+
+
+def _byte(name, v):
+    if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+        raise TypeError('RenderStyle: %s is an integer 0 .. 255, got %r' % (name, v))
+    v = int(v)
+    if not 0 <= v <= 255:
+        raise ValueError('RenderStyle: %s is 0 .. 255, got %d' % (name, v))
+    return v
+
+
+class RenderStyle:
+    """How render_frames draws the objects: per object id a colour and an opacity.  ``palette``: (256, 3) uint8 RGB, numpy or torch
+    (default: lib.image.davis_palette); ``alpha``: one 0 .. 255 opacity for all ids or a vector of 256; ``background``: None -- id 0 is left
+    untouched (a_0 = 0 whatever ``alpha`` says) -- or (r, g, b, a): dim or replace the background; ``edge_alpha``: None, or the 0 .. 255
+    opacity of an object's boundary pixels (hard rule only); ``soft``: blend by the winning mask's value instead of its label (mask stacks
+    only).  ``table``: the (256, 4) uint8 CPU rows (r, g, b, a); the device tables -- in R,G,B, or in Y,U,V of one matrix and range -- are
+    made once per (device, format) and kept."""
+
+    def __init__(self, palette=None, alpha=128, background=None, edge_alpha=None, soft=False):
+        if palette is None:
+            from .lib.image import davis_palette as palette
+        if not isinstance(palette, torch.Tensor):
+            import numpy as np
+            if not isinstance(palette, np.ndarray):
+                raise TypeError('RenderStyle: palette is a (256, 3) uint8 array or tensor, got %s' % type(palette).__name__)
+            palette = torch.from_numpy(np.ascontiguousarray(palette))
+        if palette.dtype != torch.uint8:
+            raise TypeError('RenderStyle: palette is uint8, got %s' % palette.dtype)
+        if tuple(palette.shape) != (256, 3):
+            raise ValueError('RenderStyle: palette is (256, 3), got %r' % (tuple(palette.shape),))
+        table = torch.empty(256, 4, dtype=torch.uint8)
+        table[:, :3] = palette.cpu()
+        if isinstance(alpha, numbers.Integral) and not isinstance(alpha, bool):
+            table[:, 3] = _byte('alpha', alpha)
+        else:
+            if isinstance(alpha, (bool, float, str)) or alpha is None:
+                raise TypeError('RenderStyle: alpha is an integer 0 .. 255 or 256 of them, got %r' % (alpha,))
+            a = torch.as_tensor(alpha)
+            if a.dtype.is_floating_point or a.dtype == torch.bool or a.dtype.is_complex:
+                raise TypeError('RenderStyle: alpha holds integers, got %s' % a.dtype)
+            if tuple(a.shape) != (256,):
+                raise ValueError('RenderStyle: an alpha vector has 256 entries, got %r' % (tuple(a.shape),))
+            a = a.cpu().to(torch.int64)
+            if int(a.min()) < 0 or int(a.max()) > 255:
+                raise ValueError('RenderStyle: alpha is 0 .. 255')
+            table[:, 3] = a.to(torch.uint8)
+        if background is None:
+            table[0, 3] = 0
+        else:
+            if isinstance(background, (str, bytes)) or not hasattr(background, '__len__'):
+                raise TypeError('RenderStyle: background is None or (r, g, b, a), got %r' % (background,))
+            if len(background) != 4:
+                raise ValueError('RenderStyle: background is (r, g, b, a), got %d values' % len(background))
+            table[0] = torch.tensor([_byte('background', v) for v in background], dtype=torch.uint8)
+        self.edge_alpha = None if edge_alpha is None else _byte('edge_alpha', edge_alpha)
+        if not isinstance(soft, bool):
+            raise TypeError('RenderStyle: soft is a bool, got %r' % (soft,))
+        if soft and self.edge_alpha is not None:
+            raise ValueError('RenderStyle: edge_alpha belongs to the hard rule; soft has no edges')
+        self.soft = soft
+        self.table = table
+        self._dev = {}
+
+    def table_for(self, fmt):
+        """The CPU (256, 4) uint8 table in the channels of FRAME_FORMATS id ``fmt``: (r, g, b, a) for 0, (y, u, v, a) for an NV12 format."""
+        if int(fmt) == 0:
+            return self.table
+        t = self.table.clone()
+        t[:, :3] = rgb_to_yuv_u8(self.table[:, :3], fmt)
+        return t
+
+    def device_table(self, device, fmt):
+        key = (H.normalize_device(device), int(fmt))
+        t = self._dev.get(key)
+        if t is None:
+            t = self._dev[key] = H.upload(self.table_for(fmt).contiguous(), key[0])
+        return t
+
+
+_default_style = None
+RENDER_TABLES_KEPT = 256                            # uploaded row tables render_frames keeps, least recently used first out
+_render_tables = collections.OrderedDict()
+
+
+def default_render_style():
+    global _default_style
+    if _default_style is None:
+        _default_style = RenderStyle()
+    return _default_style
+
+
+def _render_surface(what, i, f, size=None, fmt=None):
+    """(size, (FRAME_FORMATS id, tensor that holds the bytes, pitch, uv offset)) of frame / destination i; ``size`` / ``fmt``: what a destination must match."""
+    if isinstance(f, DecoderFrame):
+        got, row = tuple(f.shape[-2:]), (f.format, f.data, f.pitch, f.uv_offset)
+    else:
+        if not isinstance(f, torch.Tensor) or f.dtype != torch.uint8 or f.dim() != 3 or f.shape[0] != 3:
+            raise TypeError('render_frames: %s %d is a (3, H, W) uint8 tensor or an ops.DecoderFrame, got %s %s'
+                            % (what, i, getattr(f, 'dtype', type(f).__name__), tuple(getattr(f, 'shape', ()))))
+        if not f.is_cuda:
+            raise RuntimeError('render_frames: %s %d is on %s; the render kernel runs on the GPU only (no CPU fallback)' % (what, i, f.device))
+        if not f.is_contiguous():
+            raise TypeError('render_frames: %s %d must be contiguous' % (what, i))
+        got, row = tuple(f.shape[-2:]), (0, f, 0, 0)
+    if size is not None and (got != size or row[0] != fmt):
+        raise ValueError('render_frames: out %d is %s of size %r, its frame %s of size %r'
+                         % (i, 'planar RGB' if row[0] == 0 else 'an NV12 surface (format %d)' % row[0], got,
+                            'planar RGB' if fmt == 0 else 'an NV12 surface (format %d)' % fmt, size))
+    return got, row
+
+
+def render_frames(frames, answers, style, luts=None, out=None):
+    """frtm_render_frames_u8: the tracked objects of every frame drawn onto it, all frames in ONE launch on the current stream; nothing
+    synchronises.  ``frames``: a list of (3, H, W) uint8 CUDA tensors and / or ops.DecoderFrames, any sizes; ``answers``: per frame a
+    (H, W) uint8 label map of object ids, or a (K, H, W) float32 merged mask stack (what track() returns) with ``luts[i]``, its K uint8
+    bytes plane -> id on the device; ``style``: an ops.RenderStyle (an NV12 frame gets its palette in the frame's own matrix and range);
+    ``out``: None -- new outputs of the same kind and layout (a new DecoderFrame keeps pitch, uv_offset, matrix and range; its padding
+    bytes are unspecified) --, ``frames`` itself -- in place --, or a list of the caller's surfaces, each the kind, size and format of
+    its frame (pitch and uv_offset its own).  -> the list of outputs.  The arithmetic, exact in integers: include/frtm_hip.h.  The
+    uploaded table of a call is kept under its rows (the last RENDER_TABLES_KEPT of them): rendering the same surfaces again uploads nothing."""
+    if not isinstance(style, RenderStyle):
+        raise TypeError('render_frames: style is an ops.RenderStyle, got %s' % type(style).__name__)
+    frames, answers = list(frames), list(answers)
+    n = len(frames)
+    if not 1 <= n <= 65535:
+        raise ValueError('render_frames: %d frames (1 .. 65535)' % n)
+    if len(answers) != n or (luts is not None and len(luts) != n) or (out is not None and len(out) != n):
+        raise ValueError('render_frames: %d frames, %d answers, %s luts, %s outputs' % (n, len(answers), luts if luts is None else len(luts),
+                                                                                         out if out is None else len(out)))
+    rows, outs = [], []
+    for i, (f, ans) in enumerate(zip(frames, answers)):
+        size, (fmt, src, pitch, uv) = _render_surface('frame', i, f)
+        if not isinstance(ans, torch.Tensor) or not ((ans.dtype == torch.uint8 and ans.dim() == 2) or (ans.dtype is _F32 and ans.dim() == 3)):
+            raise TypeError('render_frames: answer %d is a (H, W) uint8 label map or a (K, H, W) float32 mask stack, got %s %s'
+                            % (i, getattr(ans, 'dtype', type(ans).__name__), tuple(getattr(ans, 'shape', ()))))
+        if tuple(ans.shape[-2:]) != size:
+            raise ValueError('render_frames: answer %d has size %r, its frame %r' % (i, tuple(ans.shape[-2:]), size))
+        if not ans.is_cuda:
+            raise RuntimeError('render_frames: answer %d is on %s; the render kernel runs on the GPU only (no CPU fallback)' % (i, ans.device))
+        if not ans.is_contiguous():
+            raise TypeError('render_frames: answer %d must be contiguous' % i)
+        stack = ans.dim() == 3
+        K, lut = 0, None
+        if stack:
+            K = ans.shape[0]
+            lut = None if luts is None else luts[i]
+            if not 1 <= K <= MAX_MERGE_OBJECTS + 1:
+                raise ValueError('render_frames: answer %d has %d planes (1 .. %d)' % (i, K, MAX_MERGE_OBJECTS + 1))
+            if not isinstance(lut, torch.Tensor) or lut.dtype != torch.uint8 or lut.dim() != 1 or lut.numel() != K or not lut.is_cuda:
+                raise TypeError('render_frames: answer %d is a stack of %d planes and needs luts[%d], %d uint8 bytes on the device' % (i, K, i, K))
+        elif style.soft:
+            raise ValueError('render_frames: answer %d is a label map; a soft style needs the mask stack' % i)
+        if out is None:
+            if isinstance(f, DecoderFrame):
+                o = DecoderFrame(torch.empty(f.nbytes_needed, dtype=torch.uint8, device=f.device), f.height, f.width, pitch=f.pitch,
+                                 uv_offset=f.uv_offset, matrix=f.matrix, full_range=f.full_range)
+            else:
+                o = torch.empty_like(f)
+        else:
+            o = out[i]
+        _, (_, dst, dpitch, duv) = _render_surface('out', i, o, size, fmt)
+        outs.append(o)
+        rows.append([RENDER_FORMATS['rgb' if fmt == 0 else 'nv12'], size[0], size[1], H.ptr(src), src.numel(), pitch, uv, H.ptr(dst), dst.numel(), dpitch, duv,
+                     RENDER_ANSWERS['masks' if stack else 'labels'], H.ptr(ans), ans.numel() * ans.element_size(), K, H.ptr(lut) or 0,
+                     H.ptr(style.device_table(ans.device, fmt)), int(style.soft), -1 if style.edge_alpha is None else style.edge_alpha, 0])
+    # a table is a function of its rows alone (they hold the addresses), so a pipeline that renders the same surfaces tick after tick --
+    # a decoder's ring into an encoder's ring -- uploads each table once; fresh allocations (out=None) miss and upload
+    key = (answers[0].device.index,) + tuple(v for r in rows for v in r)
+    kept = _render_tables.get(key)
+    if kept is None:
+        host = torch.tensor(rows, dtype=torch.int64)
+        kept = _render_tables[key] = (host, H.upload(host, answers[0].device))
+        if len(_render_tables) > RENDER_TABLES_KEPT:
+            _render_tables.popitem(last=False)
+    else:
+        _render_tables.move_to_end(key)
+    H.call('frtm_render_frames_u8', kept[0].data_ptr(), H.ptr(kept[1]), n)
+    return outs

@@ -820,6 +820,56 @@ int frtm_resize_label_map_u8(const unsigned char* src, size_t src_bytes, const l
 int frtm_frames_to_rgb_u8(const unsigned char* src, size_t src_bytes, const long long* desc_host, const long long* desc_dev, int n,
                           unsigned char* out, int H, int W, frtm_stream_t stream);
 
+/* The way out (csrc/frame_render.hip; ops.render_frames, Tracker.render, StreamPool.render): the tracked objects of n frames of any sizes
+ * and formats rendered onto those frames in ONE launch.  The table has one row of FRTM_RENDER_ROW_WORDS 64-bit words per frame and is passed
+ * twice like the other frame tables (table_host is checked and sizes the grid, table_dev is what the kernel reads, and every workgroup checks
+ * its row again).  Rows carry ADDRESSES: a caller's surfaces are separate allocations.
+ *   { format, h, w,  src, src_bytes, src_pitch, src_uv_off,  dst, dst_bytes, dst_pitch, dst_uv_off,
+ *     form, answer, answer_bytes, K, lut,  style, soft, edge_alpha, 0 }
+ * format FRTM_RENDER_RGB: src / dst are three planes of h x w bytes (pitch and uv_off ignored); FRTM_RENDER_NV12: the Y plane at the address,
+ * rows `pitch` bytes apart, interleaved U,V at address + uv_off, rows `pitch` apart as well, pitch >= 2 * ceil(w / 2), uv_off >= pitch * h --
+ * frtm_frames_to_rgb_u8's layout, source and destination each with their own pitch and uv_off; a surface spans uv_off + pitch * ceil(h / 2)
+ * bytes (3 h w for RGB), which must not exceed its *_bytes.  1 <= h, w <= 16384.  dst is src itself with the same layout (in place) or shares
+ * no byte with it, and shares none with the answer.
+ * form FRTM_RENDER_LABELS: answer is an h x w uint8 map of object ids (K, lut ignored).  FRTM_RENDER_MASKS: answer is a 4-byte aligned
+ * (K, h, w) fp32 MERGED mask stack, 1 <= K <= 16, lut its K bytes plane -> id, decoded by frtm_masks_to_native's rule: arg = the first k
+ * with the largest m_k, id = lut[arg] if arg >= 1 and m_arg > 0.5f, else lut[0].  answer_bytes: the bytes available behind answer.
+ * style: 256 rows of 4 bytes (c0, c1, c2, a) indexed by object id, in the frame's own channels (R,G,B; or Y,U,V: see below).
+ * soft 0 or 1 (FRTM_RENDER_MASKS only); edge_alpha -1 (off) or 0 .. 255 (not with soft).
+ *
+ * Per pixel, on its three channel bytes s = (s0, s1, s2) -- R,G,B; for NV12 Y and the chroma sample (U, V) of its 2 x 2 block, replicated
+ * as by frtm_frames_to_rgb_u8 --, per channel:
+ *   mix(s, c, a) = (t + (t >> 8)) >> 8,  t = s * (255 - a) + c * a + 128     ( = round(s + (c - s) * a / 255), half up, for all s, c, a in 0 .. 255 )
+ *   hard (soft 0): out = mix(s, c_id, a_id), id the pixel's label, background included.  With edge_alpha on, a pixel whose id is not the
+ *     background's (lut[0]; 0 for a label map) uses edge_alpha instead of a_id when at least one of its 4-neighbours INSIDE the picture has
+ *     another label (the picture's own border makes no edge).
+ *   soft: k* = the first k >= 1 with the largest m_k (a NaN is never the largest), m = fminf(fmaxf(m_k*, 0), 1); no such plane (K = 1,
+ *     NaNs only): m = 0.  B = mix(s, c_b, a_b), b = lut[0]; F = mix(s, c_f, a_f), f = lut[k*];
+ *     out = (int)rintf(fmaf(m, (float)(F - B), (float)B)): one fused multiply-add, one rounding to nearest even.  m in {0, 1}: the hard rule.
+ * NV12 output: Y' is the per-pixel result; chroma sample (j, i) covers the cnt = 1, 2 or 4 picture pixels of rows 2j .. min(2j + 1, h - 1),
+ * columns 2i .. min(2i + 1, w - 1): U' = (the sum of their U results + cnt / 2) / cnt, V' likewise.  A block in which nothing changes keeps
+ * its bytes; a style whose every a is 0 is the identity.  Loads and stores touch picture samples only, in src and in dst: never a byte of the
+ * row padding or of the rows between the picture and the coded height.
+ *
+ * The kernel knows no colour matrix: for an NV12 frame the caller converts its RGB palette once, by the forward formula that belongs to the
+ * inverse one of frtm_frames_to_rgb_u8 (coefficients round(65536 * the standard forward coefficient), >> the arithmetic shift):
+ *   Y = clamp(y0 + ((yr R + yg G + yb B + 32768) >> 16)),  U = clamp(128 + ((ur R + ug G + ub B + 32768) >> 16)),
+ *   V = clamp(128 + ((vr R + vg G + vb B + 32768) >> 16)),  clamp to 0 .. 255
+ *   matrix and range    y0     yr     yg    yb      ur      ug     ub     vr      vg     vb
+ *   BT601               16  16829  33039  6416   -9714  -19071  28784  28784  -24103  -4681
+ *   BT601_FULL           0  19595  38470  7471  -11058  -21710  32768  32768  -27439  -5329
+ *   BT709               16  11966  40254  4064   -6596  -22189  28784  28784  -26145  -2639
+ *   BT709_FULL           0  13933  46871  4732   -7509  -25259  32768  32768  -29763  -3005
+ * Refused with FRTM_ERR_ARG and a message before any launch: a null table or address, n outside 1 .. 65535, an unknown format or form, a
+ * size outside 1 .. 16384, K outside 1 .. 16, a pitch below a chroma row, a surface or an answer that leaves its buffer, a misaligned mask
+ * stack, a partial overlap, soft with a label map or with edge_alpha. */
+#define FRTM_RENDER_RGB 0
+#define FRTM_RENDER_NV12 1
+#define FRTM_RENDER_LABELS 0
+#define FRTM_RENDER_MASKS 1
+#define FRTM_RENDER_ROW_WORDS 20
+int frtm_render_frames_u8(const long long* table_host, const long long* table_dev, int n, frtm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
