@@ -164,6 +164,7 @@ SIGNATURES = {
     'frtm_resize_label_map_u8': (I, [P, ctypes.c_size_t, P, P, I, P, I, I, P]),
     'frtm_frames_to_rgb_u8': (I, [P, ctypes.c_size_t, P, P, I, P, I, I, P]),
     'frtm_render_frames_u8': (I, [P, P, I, P]),
+    'frtm_describe_frames': (I, [P, P, I, P, ctypes.c_size_t, P]),
 }
 
 _lib = None

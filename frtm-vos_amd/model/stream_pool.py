@@ -146,6 +146,10 @@ class StreamPool:
         # sid -> (H, W) uint8 label map (object ids, as Tracker.native_labels) at native size, for the streams whose LAST step went the way back
         # from the working size; a stream whose last step answered with its current_masks (frame at the working size, or no option) has no entry
         self.native_labels = {}
+        # sid -> (that label map, the stream's (K, H, W) native planes of the same group launch): describe() reads the planes while the entry's
+        # label map is still the stream's ``native_labels`` entry (a later step of another kind leaves this entry behind, and it is ignored)
+        self._native_planes = {}
+        self.describe_launches = 0      # ops.describe_frames launches made by describe() so far: one per call (diagnostics)
 
     # ---- streams ------------------------------------------------------------------------------------------------------------
     def open(self):
@@ -273,6 +277,29 @@ class StreamPool:
         self.render_launches += 1
         return dict(zip(sids, done))
 
+    @torch.no_grad()
+    def describe(self, sids=None, out=None):
+        """The objects of the last answer of every stream named measured -- area, box, centroid sums, edge and border pixels, confidence,
+        soft area --: -> ({sid: index}, ops.ObjectReport), ONE ops.describe_frames launch for all of them whatever their sizes and object
+        counts.  ``sids``: None -- every stream that has an answer -- or the streams to measure.  Every stream is measured on the stack its
+        last step returned (its ``current_masks``, or its native-size planes when that step went the way back from the working size) with
+        its object LUT.  ``out``: a report whose buffer is used again."""
+        if sids is None:
+            sids = [sid for sid, st in self._streams.items() if st.tracker.current_masks is not None]
+        sids = list(sids)
+        if not sids:
+            raise ValueError('StreamPool.describe: no stream has an answer (nothing was tracked)')
+        stacks, luts = [], []
+        for sid in sids:
+            labels = self.native_labels.get(sid)
+            kept = self._native_planes.get(sid)
+            stack, lut = self._streams[sid].tracker.describe_answer(labels, kept[1] if kept is not None and kept[0] is labels else None)
+            stacks.append(stack)
+            luts.append(lut)
+        report = ops.describe_frames(stacks, luts=luts, out=out)
+        self.describe_launches += 1
+        return {sid: i for i, sid in enumerate(sids)}, report
+
     def _resize_batch(self, tb, natives, frames, batch):
         """The tick's frames, of any sizes, into ``batch`` (B,3,h,w) at the working size: copied into ONE packed staging buffer (16-byte
         aligned offsets) and resized by ONE launch, mode 'area' (the identity, bit for bit, for a frame that has the working size)."""
@@ -352,6 +379,7 @@ class StreamPool:
         for r, i in enumerate(rows_of):
             out[sids[i]] = table.soft_of(soft, r)
             self.native_labels[sids[i]] = table.labels_of(labels, r)
+            self._native_planes[sids[i]] = (self.native_labels[sids[i]], out[sids[i]])
 
     def _plane_ids(self, sid, K):
         """Object id of each of stream ``sid``'s K mask planes (plane 0: the background, id 0)."""

@@ -1141,6 +1141,33 @@ class Tracker(nn.Module):
         return ops.render_frames([image], [answer], ops.default_render_style() if style is None else style, luts=[lut],
                                  out=None if out is None else [out])[0]
 
+    def describe_answer(self, labels, planes=None):
+        """(stack, lut) of ops.describe_frames for the last answer: ``current_masks`` -- or, when the last step went the way back from the
+        working size (``labels``: its native label map, ``native_labels`` or a pool's entry for the stream), the native-size planes that
+        step returned: ``planes`` when the caller kept them, else the ones _to_native keeps per shape -- with the object LUT."""
+        masks = self.current_masks
+        if masks is None:
+            raise ValueError('describe: no answer (the last step answered at no size: nothing was tracked)')
+        K = masks.shape[0]
+        if K != len(self.targets) + 1:
+            raise ValueError('describe: the last answer has %d planes, the tracker %d objects' % (K, len(self.targets)))
+        if labels is None:
+            return masks.contiguous(), self._object_lut()
+        native = tuple(int(v) for v in labels.shape[-2:])
+        if planes is None:
+            kept = self._native_bufs.get((1, K, native, True))
+            if kept is None:
+                raise ValueError('describe: no answer of size %r with %d planes (the last step answered at %r)' % (native, K, tuple(masks.shape[-2:])))
+            planes = kept[1].view(K, *native)
+        return planes, self._object_lut()
+
+    @torch.no_grad()
+    def describe(self, out=None):
+        """The objects of the last answer of track() measured in one launch (ops.describe_frames on the stack track() returned and the
+        object LUT): -> an ops.ObjectReport of one frame; ``out``: a report whose buffer is used again."""
+        stack, lut = self.describe_answer(self.native_labels)
+        return ops.describe_frames([stack], luts=[lut], out=out)
+
     def _track(self, image, features, im_size):
         if self._unchecked_fits and not self._in_run_sequence:
             self._check_first_frame_fits()

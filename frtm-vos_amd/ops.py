@@ -1248,3 +1248,147 @@ def render_frames(frames, answers, style, luts=None, out=None):
         _render_tables.move_to_end(key)
     H.call('frtm_render_frames_u8', kept[0].data_ptr(), H.ptr(kept[1]), n)
     return outs
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# Tracked objects measured on the device: boxes, areas, confidence in one launch (csrc/object_report.hip)
+# ----------------------------------------------------------------------------------------------------------------------
+OBJECT_ANSWERS = {'labels': 0, 'masks': 1}          # FRTM_OBJECT_LABELS / FRTM_OBJECT_MASKS
+OBJECT_ROW_WORDS = 8                                # FRTM_OBJECT_ROW_WORDS
+OBJECT_SLOTS = 16                                   # FRTM_OBJECT_SLOTS
+OBJECT_WORDS = 12                                   # FRTM_OBJECT_WORDS
+OBJECT_TABLES_KEPT = 256                            # uploaded row tables (with their id bytes) describe_frames keeps, least recently used first out
+_object_tables = collections.OrderedDict()
+
+ObjectStats = collections.namedtuple('ObjectStats', 'area box centroid edge border confidence soft_area')
+ObjectStats.__doc__ = """One object of one frame (ObjectReport.objects): ``area`` pixels; ``box`` (x_min, y_min, x_max, y_max), inclusive, None when
+the object has no pixel; ``centroid`` (x, y), None when empty; ``edge`` pixels with a 4-neighbour of another label inside the picture;
+``border`` pixels on the picture's border; ``confidence`` the mean of the object's mask over its pixels, in 0 .. 1 (None for a label map or
+when empty); ``soft_area`` the sum of the object's mask over the whole picture (None for a label map)."""
+
+
+class ObjectReport:
+    """What describe_frames measured: ``words``, the (n, 16, 12) int64 tensor of include/frtm_hip.h (on the device: making the report does
+    not synchronise), with ``K[i]`` slots of frame i in use and ``stacks[i]`` True when frame i was a mask stack.  ``cpu()`` makes the one
+    device-to-host copy (1.5 KB per frame) and keeps it; ``objects(i)`` -> {object id: ObjectStats} of frame i from that copy."""
+
+    def __init__(self, words, K, stacks):
+        if not isinstance(words, torch.Tensor) or words.dtype != torch.int64 or words.dim() != 3 or tuple(words.shape[1:]) != (OBJECT_SLOTS, OBJECT_WORDS):
+            raise TypeError('ObjectReport: words is a (n, %d, %d) int64 tensor, got %s %s'
+                            % (OBJECT_SLOTS, OBJECT_WORDS, getattr(words, 'dtype', type(words).__name__), tuple(getattr(words, 'shape', ()))))
+        K, stacks = [int(k) for k in K], [bool(s) for s in stacks]
+        if len(K) != words.shape[0] or len(stacks) != words.shape[0] or any(not 1 <= k <= OBJECT_SLOTS for k in K):
+            raise ValueError('ObjectReport: %d frames, %d slot counts (1 .. %d), %d forms' % (words.shape[0], len(K), OBJECT_SLOTS, len(stacks)))
+        self.words, self.K, self.stacks = words, K, stacks
+        self._host = None
+
+    def __len__(self):
+        return self.words.shape[0]
+
+    def cpu(self):
+        if self._host is None:
+            self._host = self.words.cpu()
+        return self._host
+
+    def objects(self, i):
+        out = {}
+        for area, x0, y0, x1, y1, sx, sy, edge, border, conf, mass, oid in self.cpu()[i, :self.K[i]].tolist():
+            stack = self.stacks[i]
+            out[oid] = ObjectStats(area, (x0, y0, x1, y1) if area else None, (sx / area, sy / area) if area else None, edge, border,
+                                   conf / (255.0 * area) if stack and area else None, mass / 255.0 if stack else None)
+        return out
+
+
+def _object_ids(i, ids):
+    if isinstance(ids, (str, bytes)) or not hasattr(ids, '__len__') or not hasattr(ids, '__iter__'):
+        raise TypeError('describe_frames: answer %d is a label map and needs ids[%d], a sequence of distinct ints in 0 .. 255, got %r' % (i, i, ids))
+    ids = list(ids.tolist() if isinstance(ids, torch.Tensor) else ids)
+    if any(isinstance(v, bool) or not isinstance(v, numbers.Integral) for v in ids):
+        raise TypeError('describe_frames: ids[%d] holds ints, got %r' % (i, ids))
+    ids = tuple(int(v) for v in ids)
+    if not 1 <= len(ids) <= OBJECT_SLOTS:
+        raise ValueError('describe_frames: ids[%d] lists %d ids (1 .. %d)' % (i, len(ids), OBJECT_SLOTS))
+    if any(not 0 <= v <= 255 for v in ids):
+        raise ValueError('describe_frames: ids[%d] is 0 .. 255, got %r' % (i, ids))
+    if len(set(ids)) != len(ids):
+        raise ValueError('describe_frames: ids[%d] lists an id twice: %r' % (i, ids))
+    return ids
+
+
+def describe_frames(answers, luts=None, ids=None, out=None):
+    """frtm_describe_frames: the objects of every frame measured -- area, box, coordinate sums, edge and border pixels, confidence and soft
+    area --, all frames in ONE launch on the current stream; nothing synchronises.  ``answers``: per frame a (H, W) uint8 label map of
+    object ids with ``ids[i]``, a sequence of at most 16 distinct ints in 0 .. 255 to measure (uploaded once and kept with the table), or a
+    (K, H, W) float32 merged mask stack (what track() returns) with ``luts[i]``, its K uint8 bytes plane -> id on the device; any sizes,
+    both kinds mixed.  ``out``: None, or an ObjectReport (or an int64 device tensor) whose buffer of at least n x 16 x 12 words is used
+    again; only its first n x 16 x 12 words are written.  -> an ObjectReport.  The words, exact in integers: include/frtm_hip.h."""
+    answers = list(answers)
+    n = len(answers)
+    if not 1 <= n <= 65535:
+        raise ValueError('describe_frames: %d frames (1 .. 65535)' % n)
+    if (luts is not None and len(luts) != n) or (ids is not None and len(ids) != n):
+        raise ValueError('describe_frames: %d answers, %s luts, %s ids' % (n, luts if luts is None else len(luts), ids if ids is None else len(ids)))
+    frames, Ks, stacks = [], [], []
+    for i, ans in enumerate(answers):
+        if not isinstance(ans, torch.Tensor) or not ((ans.dtype == torch.uint8 and ans.dim() == 2) or (ans.dtype is _F32 and ans.dim() == 3)):
+            raise TypeError('describe_frames: answer %d is a (H, W) uint8 label map or a (K, H, W) float32 mask stack, got %s %s'
+                            % (i, getattr(ans, 'dtype', type(ans).__name__), tuple(getattr(ans, 'shape', ()))))
+        h, w = (int(v) for v in ans.shape[-2:])
+        if not (1 <= h <= MAX_NATIVE_DIM and 1 <= w <= MAX_NATIVE_DIM):
+            raise ValueError('describe_frames: answer %d has size %d x %d (1 .. %d)' % (i, h, w, MAX_NATIVE_DIM))
+        stack = ans.dim() == 3
+        if stack:
+            K = int(ans.shape[0])
+            lut = None if luts is None else luts[i]
+            if not 1 <= K <= MAX_MERGE_OBJECTS + 1:
+                raise ValueError('describe_frames: answer %d has %d planes (1 .. %d)' % (i, K, MAX_MERGE_OBJECTS + 1))
+            if not isinstance(lut, torch.Tensor) or lut.dtype != torch.uint8 or lut.dim() != 1 or lut.numel() != K or not lut.is_cuda:
+                raise TypeError('describe_frames: answer %d is a stack of %d planes and needs luts[%d], %d uint8 bytes on the device' % (i, K, i, K))
+            which = lut
+        else:
+            which = _object_ids(i, None if ids is None else ids[i])
+            K = len(which)
+        if not ans.is_cuda:
+            raise RuntimeError('describe_frames: answer %d is on %s; the report kernel runs on the GPU only (no CPU fallback)' % (i, ans.device))
+        if not ans.is_contiguous():
+            raise TypeError('describe_frames: answer %d must be contiguous' % i)
+        frames.append((stack, h, w, ans, K, which))
+        Ks.append(K)
+        stacks.append(stack)
+    device = answers[0].device
+    need = n * OBJECT_SLOTS * OBJECT_WORDS
+    if out is None:
+        words = torch.empty(n, OBJECT_SLOTS, OBJECT_WORDS, dtype=torch.int64, device=device)
+    else:
+        words = out.words if isinstance(out, ObjectReport) else out
+        if not isinstance(words, torch.Tensor) or words.dtype != torch.int64:
+            raise TypeError('describe_frames: out is an ops.ObjectReport or an int64 tensor, got %s' % getattr(words, 'dtype', type(words).__name__))
+        if not words.is_cuda:
+            raise RuntimeError('describe_frames: out is on %s; the report kernel runs on the GPU only (no CPU fallback)' % (words.device,))
+        if not words.is_contiguous():
+            raise TypeError('describe_frames: out must be contiguous')
+        if words.numel() < need:
+            raise ValueError('describe_frames: out holds %d words, %d frames need %d' % (words.numel(), n, need))
+    # a table is a function of its rows (they hold the addresses) and of the ids to measure, so a pipeline that describes the same buffers tick
+    # after tick uploads the table and the id bytes once
+    key = (device.index,) + tuple((stack, h, w, H.ptr(ans), ans.numel() * ans.element_size(), K, H.ptr(which) if stack else which)
+                                  for stack, h, w, ans, K, which in frames)
+    kept = _object_tables.get(key)
+    if kept is None:
+        id_bytes = None
+        if not all(stacks):
+            host_ids = torch.zeros(n, OBJECT_SLOTS, dtype=torch.uint8)
+            for i, (stack, _, _, _, K, which) in enumerate(frames):
+                if not stack:
+                    host_ids[i, :K] = torch.tensor(which, dtype=torch.uint8)
+            id_bytes = H.upload(host_ids, device)
+        rows = [[OBJECT_ANSWERS['masks' if stack else 'labels'], h, w, H.ptr(ans), ans.numel() * ans.element_size(), K,
+                 H.ptr(which) if stack else id_bytes.data_ptr() + OBJECT_SLOTS * i, 0] for i, (stack, h, w, ans, K, which) in enumerate(frames)]
+        host = torch.tensor(rows, dtype=torch.int64)
+        kept = _object_tables[key] = (host, H.upload(host, device), id_bytes)
+        if len(_object_tables) > OBJECT_TABLES_KEPT:
+            _object_tables.popitem(last=False)
+    else:
+        _object_tables.move_to_end(key)
+    H.call('frtm_describe_frames', kept[0].data_ptr(), H.ptr(kept[1]), n, H.ptr(words), words.numel())
+    return ObjectReport(words.view(-1)[:need].view(n, OBJECT_SLOTS, OBJECT_WORDS), Ks, stacks)

@@ -870,6 +870,47 @@ int frtm_frames_to_rgb_u8(const unsigned char* src, size_t src_bytes, const long
 #define FRTM_RENDER_ROW_WORDS 20
 int frtm_render_frames_u8(const long long* table_host, const long long* table_dev, int n, frtm_stream_t stream);
 
+/* The numbers a program needs to ACT on the answer (csrc/object_report.hip; ops.describe_frames, Tracker.describe, StreamPool.describe): the
+ * tracked objects of n frames of any sizes measured in ONE launch, label maps and mask stacks mixed.  The conventions are
+ * frtm_render_frames_u8's: the table is passed twice (table_host is checked and sizes the grid, table_dev is what the kernels read, and every
+ * workgroup checks its row again), rows carry ADDRESSES, everything is enqueued on `stream` and nothing synchronises.  A row is
+ * FRTM_OBJECT_ROW_WORDS 64-bit words:
+ *   { form, h, w, answer, answer_bytes, K, ids, 0 }
+ * form FRTM_OBJECT_LABELS: answer is an h x w uint8 map of object ids; ids: the address of the K DISTINCT ids to measure (a precondition: the
+ * host cannot read device bytes; if an id is listed twice the first slot that lists it takes the pixel).  FRTM_OBJECT_MASKS: answer is a 4-byte
+ * aligned (K, h, w) fp32 MERGED mask stack, ids its K bytes plane -> id.  1 <= K <= 16, 1 <= h, w <= 16384; answer_bytes: the bytes available
+ * behind answer.
+ * The slot of a pixel.  Stack: the decoded plane of frtm_masks_to_native's rule: arg = the first k with the largest m_k (a NaN never wins), slot
+ * = arg if arg >= 1 and m_arg > 0.5f, else 0.  Label map: the index of the pixel's id in ids; a pixel whose id is not listed has no slot.
+ * The label of a pixel (for edges): the decoded plane, or the id of a label map -- an unlisted id is still another label.
+ * out: n x 16 x FRTM_OBJECT_WORDS 64-bit words, frame-major then slot; out_words (the words available behind out) must be at least that many.
+ * The words of slot s < K of a frame (slots s >= K: twelve zeros):
+ *   0      area     pixels of the slot
+ *   1 .. 4 x_min, y_min, x_max, y_max   the inclusive box; of an empty slot w, h, -1, -1
+ *   5, 6   sum_x, sum_y   sums of the coordinates of the slot's pixels (centroid = sum / area)
+ *   7      edge     pixels of the slot with at least one 4-neighbour INSIDE the picture that has another label (the renderer's edge rule, for
+ *                   every slot, slot 0 included; the picture's own border makes no edge)
+ *   8      border   pixels of the slot on row 0, row h - 1, column 0 or column w - 1 (a corner counts once)
+ *   9      conf     stacks: the sum over the slot's pixels of q(m_slot), q(m) = (long long)rintf(255.0f * fminf(fmaxf(m, 0.0f), 1.0f)), a NaN
+ *                   gives 0; label maps: 0
+ *   10     mass     stacks: the sum over ALL pixels of q(m_s) of plane s (255 x the soft area: above zero while a fading object's area is 0
+ *                   already); label maps: 0
+ *   11     id       ids[s]
+ * All accumulation is in integers (64-bit in memory: sum_x reaches 2^42, conf 2^36), hence independent of order and deterministic; no float
+ * atomics.  A call enqueues exactly TWO operations on `stream`: the kernel that writes the start of every word (zeros, the empty box, the ids)
+ * and the kernel that measures, with one integer atomic per workgroup and word.  Loads touch picture samples and the K id bytes only; stores
+ * touch the n x 16 x 12 words only.
+ * Refused with FRTM_ERR_ARG and a message before anything is enqueued, out untouched: a null table, address or out, n outside 1 .. 65535, an
+ * unknown form, a size outside 1 .. 16384, K outside 1 .. 16, an answer that leaves answer_bytes, a misaligned stack, out_words too small, a
+ * non-zero last word. */
+#define FRTM_OBJECT_LABELS 0
+#define FRTM_OBJECT_MASKS 1
+#define FRTM_OBJECT_ROW_WORDS 8
+#define FRTM_OBJECT_SLOTS 16
+#define FRTM_OBJECT_WORDS 12
+int frtm_describe_frames(const long long* table_host, const long long* table_dev, int n, long long* out, size_t out_words,
+                         frtm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
