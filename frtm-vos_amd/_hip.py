@@ -165,6 +165,8 @@ SIGNATURES = {
     'frtm_frames_to_rgb_u8': (I, [P, ctypes.c_size_t, P, P, I, P, I, I, P]),
     'frtm_render_frames_u8': (I, [P, P, I, P]),
     'frtm_describe_frames': (I, [P, P, I, P, ctypes.c_size_t, P]),
+    'frtm_encode_work_bytes': (ctypes.c_size_t, [P, I, ctypes.c_size_t]),
+    'frtm_encode_frames': (I, [P, P, I, P, ctypes.c_size_t, P, ctypes.c_size_t, P, ctypes.c_size_t, P]),
 }
 
 _lib = None

@@ -10,9 +10,7 @@
 // from the bit planes of the lane number and of q), they ride in lanes (lane 4 s + c, three registers: word 4 r + c of slot s), the four waves
 // are combined in LDS, then one integer atomic per workgroup and word that changed.  No float atomics: order independent, hence deterministic.
 // Loads touch picture samples and the K id bytes only; stores touch the n x 16 x 12 words only.
-#include "frtm_common.h"
-#include "per_frame.h"       // MERGE_MAX, merged_offer, merged_plane
-#include "../../include/frtm_hip.h"
+#include "object_rows.h"     // the table row and its check (shared with mask_runs.hip); MERGE_MAX, merged_offer, merged_plane through per_frame.h
 #include <climits>
 #include <cstdint>
 
@@ -22,38 +20,14 @@
 #define OB_MAX_TILES 127    // tiles per workgroup that the 32-bit sums in registers hold
 #define OB_GRID 256         // workgroups per frame, unless OB_MAX_TILES asks for more
 #define OB_CELLS 5          // label-patch cells per thread: ceil(18 * 66 / 256)
-#define OB_MAXDIM 16384
-#define OB_MAXBYTES (1LL << 46)
-#define OB_ROW FRTM_OBJECT_ROW_WORDS
-#define OB_SLOTS FRTM_OBJECT_SLOTS
 #define OB_WORDS FRTM_OBJECT_WORDS
-#define OB_NONE 255         // slot of a label-map pixel whose id is not listed
 
 static_assert(OB_SLOTS == MERGE_MAX && OB_SLOTS * 4 == 64 && OB_WORDS == 12, "lane 4 s + c holds words c, 4 + c, 8 + c of slot s");
 
 typedef unsigned long long u64;
 
-// words of a table row
-enum { OW_FORM, OW_H, OW_W, OW_ANS, OW_ANS_BYTES, OW_K, OW_IDS, OW_ZERO };
 // words of a slot
 enum { OS_AREA, OS_XMIN, OS_YMIN, OS_XMAX, OS_YMAX, OS_SUMX, OS_SUMY, OS_EDGE, OS_BORDER, OS_CONF, OS_MASS, OS_ID };
-// why a row is refused
-enum { OB_OK, OB_BAD_ENUM, OB_BAD_SIZE, OB_BAD_K, OB_NULL, OB_NOT_A_SIZE, OB_ANS_RANGE, OB_ANS_ALIGN };
-
-// Is row r a frame this launch can measure?  (Evaluated by the host from its copy, for the messages and the grid, and by every workgroup from
-// the DEVICE table before it touches anything: a device table that differs from the checked one reads nothing out of bounds.)
-__host__ __device__ static inline int ob_check(const long long* r) {
-  const long long form = r[OW_FORM], h = r[OW_H], w = r[OW_W], K = r[OW_K], ab = r[OW_ANS_BYTES];
-  if ((form != FRTM_OBJECT_LABELS && form != FRTM_OBJECT_MASKS) || r[OW_ZERO] != 0) return OB_BAD_ENUM;
-  if (h < 1 || w < 1 || h > OB_MAXDIM || w > OB_MAXDIM) return OB_BAD_SIZE;
-  if (K < 1 || K > OB_SLOTS) return OB_BAD_K;
-  if (!r[OW_ANS] || !r[OW_IDS]) return OB_NULL;
-  if (ab < 0 || ab > OB_MAXBYTES) return OB_NOT_A_SIZE;
-  if ((form == FRTM_OBJECT_MASKS ? 4 * K * h * w : h * w) > ab) return OB_ANS_RANGE;
-  if (form == FRTM_OBJECT_MASKS && (r[OW_ANS] & 3)) return OB_ANS_ALIGN;
-  return OB_OK;
-}
-
 // q(m) = rintf(255 clamp(m, 0, 1)); fmaxf returns the other operand for a NaN, so a NaN gives 0
 __device__ __forceinline__ int ob_q(float m) { return (int)rintf(255.0f * fminf(fmaxf(m, 0.0f), 1.0f)); }
 
@@ -259,22 +233,10 @@ extern "C" int frtm_describe_frames(const long long* table_host, const long long
   FRTM_CHECK_ARG(n >= 1 && n <= 65535, "%s: n = %d frames (1 .. 65535)", who, n);
   FRTM_CHECK_ARG(out_words >= (size_t)n * OB_SLOTS * OB_WORDS, "%s: out holds %zu words, %d frames need %zu", who, out_words, n,
                  (size_t)n * OB_SLOTS * OB_WORDS);
+  if (ob_check_table(who, table_host, n) != FRTM_OK) return FRTM_ERR_ARG;
   int tiles = 0;                                                         // of the launch's largest frame (<= 256 * 1024)
   for (int i = 0; i < n; ++i) {
     const long long* r = table_host + (size_t)OB_ROW * i;
-    switch (ob_check(r)) {
-      case OB_OK: break;
-      case OB_BAD_ENUM:
-        FRTM_CHECK_ARG(false, "%s: frame %d has answer form %lld and last word %lld (a form of include/frtm_hip.h, and 0)", who, i, r[OW_FORM], r[OW_ZERO]);
-      case OB_BAD_SIZE: FRTM_CHECK_ARG(false, "%s: frame %d has size %lld x %lld (1 .. %d)", who, i, r[OW_H], r[OW_W], OB_MAXDIM);
-      case OB_BAD_K: FRTM_CHECK_ARG(false, "%s: frame %d has K = %lld slots (1 .. %d)", who, i, r[OW_K], OB_SLOTS);
-      case OB_NULL: FRTM_CHECK_ARG(false, "%s: frame %d has a null address (answer %#llx, ids %#llx)", who, i, r[OW_ANS], r[OW_IDS]);
-      case OB_NOT_A_SIZE: FRTM_CHECK_ARG(false, "%s: frame %d: answer_bytes %lld is not a size", who, i, r[OW_ANS_BYTES]);
-      case OB_ANS_RANGE:
-        FRTM_CHECK_ARG(false, "%s: frame %d's answer (%lld bytes) leaves its %lld-byte buffer", who, i,
-                       r[OW_FORM] == FRTM_OBJECT_MASKS ? 4 * r[OW_K] * r[OW_H] * r[OW_W] : r[OW_H] * r[OW_W], r[OW_ANS_BYTES]);
-      default: FRTM_CHECK_ARG(false, "%s: frame %d's mask stack at %#llx is not 4-byte aligned", who, i, r[OW_ANS]);
-    }
     tiles = max(tiles, ceil_div((int)r[OW_W], OB_TW) * ceil_div((int)r[OW_H], OB_TH));
   }
   hipStream_t st = (hipStream_t)stream;

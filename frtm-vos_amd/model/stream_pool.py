@@ -150,6 +150,7 @@ class StreamPool:
         # label map is still the stream's ``native_labels`` entry (a later step of another kind leaves this entry behind, and it is ignored)
         self._native_planes = {}
         self.describe_launches = 0      # ops.describe_frames launches made by describe() so far: one per call (diagnostics)
+        self.encode_launches = 0        # ops.encode_frames launches made by encode() so far: one per call (diagnostics)
 
     # ---- streams ------------------------------------------------------------------------------------------------------------
     def open(self):
@@ -277,18 +278,13 @@ class StreamPool:
         self.render_launches += 1
         return dict(zip(sids, done))
 
-    @torch.no_grad()
-    def describe(self, sids=None, out=None):
-        """The objects of the last answer of every stream named measured -- area, box, centroid sums, edge and border pixels, confidence,
-        soft area --: -> ({sid: index}, ops.ObjectReport), ONE ops.describe_frames launch for all of them whatever their sizes and object
-        counts.  ``sids``: None -- every stream that has an answer -- or the streams to measure.  Every stream is measured on the stack its
-        last step returned (its ``current_masks``, or its native-size planes when that step went the way back from the working size) with
-        its object LUT.  ``out``: a report whose buffer is used again."""
+    def _answers(self, who, sids):
+        """(sids, stacks, luts) of the last answers of the streams named (None: every stream that has one), for describe() and encode()."""
         if sids is None:
             sids = [sid for sid, st in self._streams.items() if st.tracker.current_masks is not None]
         sids = list(sids)
         if not sids:
-            raise ValueError('StreamPool.describe: no stream has an answer (nothing was tracked)')
+            raise ValueError('StreamPool.%s: no stream has an answer (nothing was tracked)' % who)
         stacks, luts = [], []
         for sid in sids:
             labels = self.native_labels.get(sid)
@@ -296,9 +292,29 @@ class StreamPool:
             stack, lut = self._streams[sid].tracker.describe_answer(labels, kept[1] if kept is not None and kept[0] is labels else None)
             stacks.append(stack)
             luts.append(lut)
+        return sids, stacks, luts
+
+    @torch.no_grad()
+    def describe(self, sids=None, out=None):
+        """The objects of the last answer of every stream named measured -- area, box, centroid sums, edge and border pixels, confidence,
+        soft area --: -> ({sid: index}, ops.ObjectReport), ONE ops.describe_frames launch for all of them whatever their sizes and object
+        counts.  ``sids``: None -- every stream that has an answer -- or the streams to measure.  Every stream is measured on the stack its
+        last step returned (its ``current_masks``, or its native-size planes when that step went the way back from the working size) with
+        its object LUT.  ``out``: a report whose buffer is used again."""
+        sids, stacks, luts = self._answers('describe', sids)
         report = ops.describe_frames(stacks, luts=luts, out=out)
         self.describe_launches += 1
         return {sid: i for i, sid in enumerate(sids)}, report
+
+    @torch.no_grad()
+    def encode(self, sids=None, out=None, capacity=None):
+        """The objects of the last answer of every stream named as COCO run lengths, coded on the device: -> ({sid: index}, ops.MaskRuns),
+        ONE ops.encode_frames call for all of them whatever their sizes and object counts.  ``sids`` and the stack every stream is coded
+        from: describe()'s.  ``out``: a MaskRuns whose buffers are used again; ``capacity``: the elements of its ``runs``."""
+        sids, stacks, luts = self._answers('encode', sids)
+        coded = ops.encode_frames(stacks, luts=luts, out=out, capacity=capacity)
+        self.encode_launches += 1
+        return {sid: i for i, sid in enumerate(sids)}, coded
 
     def _resize_batch(self, tb, natives, frames, batch):
         """The tick's frames, of any sizes, into ``batch`` (B,3,h,w) at the working size: copied into ONE packed staging buffer (16-byte

@@ -1168,6 +1168,14 @@ class Tracker(nn.Module):
         stack, lut = self.describe_answer(self.native_labels)
         return ops.describe_frames([stack], luts=[lut], out=out)
 
+    @torch.no_grad()
+    def encode(self, out=None, capacity=None):
+        """The objects of the last answer of track() as COCO run lengths, coded on the device (ops.encode_frames on the stack track() returned
+        -- under ``working_size`` the native-size stack -- and the object LUT): -> an ops.MaskRuns of one frame; ``out``: a MaskRuns whose
+        buffers are used again; ``capacity``: the elements of its ``runs`` (default: K (8 w + 8))."""
+        stack, lut = self.describe_answer(self.native_labels)
+        return ops.encode_frames([stack], luts=[lut], out=out, capacity=capacity)
+
     def _track(self, image, features, im_size):
         if self._unchecked_fits and not self._in_run_sequence:
             self._check_first_frame_fits()

@@ -1299,84 +1299,69 @@ class ObjectReport:
         return out
 
 
-def _object_ids(i, ids):
+def _object_ids(i, ids, who='describe_frames'):
     if isinstance(ids, (str, bytes)) or not hasattr(ids, '__len__') or not hasattr(ids, '__iter__'):
-        raise TypeError('describe_frames: answer %d is a label map and needs ids[%d], a sequence of distinct ints in 0 .. 255, got %r' % (i, i, ids))
+        raise TypeError(who + ': answer %d is a label map and needs ids[%d], a sequence of distinct ints in 0 .. 255, got %r' % (i, i, ids))
     ids = list(ids.tolist() if isinstance(ids, torch.Tensor) else ids)
     if any(isinstance(v, bool) or not isinstance(v, numbers.Integral) for v in ids):
-        raise TypeError('describe_frames: ids[%d] holds ints, got %r' % (i, ids))
+        raise TypeError(who + ': ids[%d] holds ints, got %r' % (i, ids))
     ids = tuple(int(v) for v in ids)
     if not 1 <= len(ids) <= OBJECT_SLOTS:
-        raise ValueError('describe_frames: ids[%d] lists %d ids (1 .. %d)' % (i, len(ids), OBJECT_SLOTS))
+        raise ValueError(who + ': ids[%d] lists %d ids (1 .. %d)' % (i, len(ids), OBJECT_SLOTS))
     if any(not 0 <= v <= 255 for v in ids):
-        raise ValueError('describe_frames: ids[%d] is 0 .. 255, got %r' % (i, ids))
+        raise ValueError(who + ': ids[%d] is 0 .. 255, got %r' % (i, ids))
     if len(set(ids)) != len(ids):
-        raise ValueError('describe_frames: ids[%d] lists an id twice: %r' % (i, ids))
+        raise ValueError(who + ': ids[%d] lists an id twice: %r' % (i, ids))
     return ids
 
 
-def describe_frames(answers, luts=None, ids=None, out=None):
-    """frtm_describe_frames: the objects of every frame measured -- area, box, coordinate sums, edge and border pixels, confidence and soft
-    area --, all frames in ONE launch on the current stream; nothing synchronises.  ``answers``: per frame a (H, W) uint8 label map of
-    object ids with ``ids[i]``, a sequence of at most 16 distinct ints in 0 .. 255 to measure (uploaded once and kept with the table), or a
-    (K, H, W) float32 merged mask stack (what track() returns) with ``luts[i]``, its K uint8 bytes plane -> id on the device; any sizes,
-    both kinds mixed.  ``out``: None, or an ObjectReport (or an int64 device tensor) whose buffer of at least n x 16 x 12 words is used
-    again; only its first n x 16 x 12 words are written.  -> an ObjectReport.  The words, exact in integers: include/frtm_hip.h."""
+def _object_frames(who, answers, luts, ids):
+    """The per-answer checks describe_frames and encode_frames share -> (frames: per answer (stack, h, w, tensor, K, LUT or ids), device)."""
     answers = list(answers)
     n = len(answers)
     if not 1 <= n <= 65535:
-        raise ValueError('describe_frames: %d frames (1 .. 65535)' % n)
+        raise ValueError(who + ': %d frames (1 .. 65535)' % n)
     if (luts is not None and len(luts) != n) or (ids is not None and len(ids) != n):
-        raise ValueError('describe_frames: %d answers, %s luts, %s ids' % (n, luts if luts is None else len(luts), ids if ids is None else len(ids)))
-    frames, Ks, stacks = [], [], []
+        raise ValueError(who + ': %d answers, %s luts, %s ids' % (n, luts if luts is None else len(luts), ids if ids is None else len(ids)))
+    frames = []
     for i, ans in enumerate(answers):
         if not isinstance(ans, torch.Tensor) or not ((ans.dtype == torch.uint8 and ans.dim() == 2) or (ans.dtype is _F32 and ans.dim() == 3)):
-            raise TypeError('describe_frames: answer %d is a (H, W) uint8 label map or a (K, H, W) float32 mask stack, got %s %s'
+            raise TypeError(who + ': answer %d is a (H, W) uint8 label map or a (K, H, W) float32 mask stack, got %s %s'
                             % (i, getattr(ans, 'dtype', type(ans).__name__), tuple(getattr(ans, 'shape', ()))))
         h, w = (int(v) for v in ans.shape[-2:])
         if not (1 <= h <= MAX_NATIVE_DIM and 1 <= w <= MAX_NATIVE_DIM):
-            raise ValueError('describe_frames: answer %d has size %d x %d (1 .. %d)' % (i, h, w, MAX_NATIVE_DIM))
+            raise ValueError(who + ': answer %d has size %d x %d (1 .. %d)' % (i, h, w, MAX_NATIVE_DIM))
         stack = ans.dim() == 3
         if stack:
             K = int(ans.shape[0])
             lut = None if luts is None else luts[i]
             if not 1 <= K <= MAX_MERGE_OBJECTS + 1:
-                raise ValueError('describe_frames: answer %d has %d planes (1 .. %d)' % (i, K, MAX_MERGE_OBJECTS + 1))
+                raise ValueError(who + ': answer %d has %d planes (1 .. %d)' % (i, K, MAX_MERGE_OBJECTS + 1))
             if not isinstance(lut, torch.Tensor) or lut.dtype != torch.uint8 or lut.dim() != 1 or lut.numel() != K or not lut.is_cuda:
-                raise TypeError('describe_frames: answer %d is a stack of %d planes and needs luts[%d], %d uint8 bytes on the device' % (i, K, i, K))
+                raise TypeError(who + ': answer %d is a stack of %d planes and needs luts[%d], %d uint8 bytes on the device' % (i, K, i, K))
             which = lut
         else:
-            which = _object_ids(i, None if ids is None else ids[i])
+            which = _object_ids(i, None if ids is None else ids[i], who)
             K = len(which)
         if not ans.is_cuda:
-            raise RuntimeError('describe_frames: answer %d is on %s; the report kernel runs on the GPU only (no CPU fallback)' % (i, ans.device))
+            raise RuntimeError(who + ': answer %d is on %s; the kernel runs on the GPU only (no CPU fallback)' % (i, ans.device))
         if not ans.is_contiguous():
-            raise TypeError('describe_frames: answer %d must be contiguous' % i)
+            raise TypeError(who + ': answer %d must be contiguous' % i)
         frames.append((stack, h, w, ans, K, which))
-        Ks.append(K)
-        stacks.append(stack)
-    device = answers[0].device
-    need = n * OBJECT_SLOTS * OBJECT_WORDS
-    if out is None:
-        words = torch.empty(n, OBJECT_SLOTS, OBJECT_WORDS, dtype=torch.int64, device=device)
-    else:
-        words = out.words if isinstance(out, ObjectReport) else out
-        if not isinstance(words, torch.Tensor) or words.dtype != torch.int64:
-            raise TypeError('describe_frames: out is an ops.ObjectReport or an int64 tensor, got %s' % getattr(words, 'dtype', type(words).__name__))
-        if not words.is_cuda:
-            raise RuntimeError('describe_frames: out is on %s; the report kernel runs on the GPU only (no CPU fallback)' % (words.device,))
-        if not words.is_contiguous():
-            raise TypeError('describe_frames: out must be contiguous')
-        if words.numel() < need:
-            raise ValueError('describe_frames: out holds %d words, %d frames need %d' % (words.numel(), n, need))
-    # a table is a function of its rows (they hold the addresses) and of the ids to measure, so a pipeline that describes the same buffers tick
-    # after tick uploads the table and the id bytes once
+    return frames, answers[0].device
+
+
+def _object_table(frames, device):
+    """The uploaded row table of ``frames`` -> (host table, device table, id bytes): a table is a function of its rows (they hold the
+    addresses) and of the ids to measure, so a pipeline that describes or encodes the same buffers tick after tick uploads the table and the
+    id bytes once; describe_frames and encode_frames read the same row, so they share the entries."""
+    n = len(frames)
     key = (device.index,) + tuple((stack, h, w, H.ptr(ans), ans.numel() * ans.element_size(), K, H.ptr(which) if stack else which)
                                   for stack, h, w, ans, K, which in frames)
     kept = _object_tables.get(key)
     if kept is None:
         id_bytes = None
-        if not all(stacks):
+        if not all(f[0] for f in frames):
             host_ids = torch.zeros(n, OBJECT_SLOTS, dtype=torch.uint8)
             for i, (stack, _, _, _, K, which) in enumerate(frames):
                 if not stack:
@@ -1390,5 +1375,194 @@ def describe_frames(answers, luts=None, ids=None, out=None):
             _object_tables.popitem(last=False)
     else:
         _object_tables.move_to_end(key)
+    return kept
+
+
+def describe_frames(answers, luts=None, ids=None, out=None):
+    """frtm_describe_frames: the objects of every frame measured -- area, box, coordinate sums, edge and border pixels, confidence and soft
+    area --, all frames in ONE launch on the current stream; nothing synchronises.  ``answers``: per frame a (H, W) uint8 label map of
+    object ids with ``ids[i]``, a sequence of at most 16 distinct ints in 0 .. 255 to measure (uploaded once and kept with the table), or a
+    (K, H, W) float32 merged mask stack (what track() returns) with ``luts[i]``, its K uint8 bytes plane -> id on the device; any sizes,
+    both kinds mixed.  ``out``: None, or an ObjectReport (or an int64 device tensor) whose buffer of at least n x 16 x 12 words is used
+    again; only its first n x 16 x 12 words are written.  -> an ObjectReport.  The words, exact in integers: include/frtm_hip.h."""
+    frames, device = _object_frames('describe_frames', answers, luts, ids)
+    n = len(frames)
+    Ks, stacks = [f[4] for f in frames], [f[0] for f in frames]
+    need = n * OBJECT_SLOTS * OBJECT_WORDS
+    if out is None:
+        words = torch.empty(n, OBJECT_SLOTS, OBJECT_WORDS, dtype=torch.int64, device=device)
+    else:
+        words = out.words if isinstance(out, ObjectReport) else out
+        if not isinstance(words, torch.Tensor) or words.dtype != torch.int64:
+            raise TypeError('describe_frames: out is an ops.ObjectReport or an int64 tensor, got %s' % getattr(words, 'dtype', type(words).__name__))
+        if not words.is_cuda:
+            raise RuntimeError('describe_frames: out is on %s; the report kernel runs on the GPU only (no CPU fallback)' % (words.device,))
+        if not words.is_contiguous():
+            raise TypeError('describe_frames: out must be contiguous')
+        if words.numel() < need:
+            raise ValueError('describe_frames: out holds %d words, %d frames need %d' % (words.numel(), n, need))
+    kept = _object_table(frames, device)
     H.call('frtm_describe_frames', kept[0].data_ptr(), H.ptr(kept[1]), n, H.ptr(words), words.numel())
     return ObjectReport(words.view(-1)[:need].view(n, OBJECT_SLOTS, OBJECT_WORDS), Ks, stacks)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# Tracked masks coded on the device: COCO run lengths per object (csrc/mask_runs.hip)
+# ----------------------------------------------------------------------------------------------------------------------
+RUNS_HEAD_WORDS = 4                                 # FRTM_RUNS_HEAD_WORDS: { count, offset, area, id }
+RUNS_MAX_CAPACITY = 1 << 40
+
+
+class RunsOverflow(ValueError):
+    """MaskRuns.cpu(): the lists need ``needed`` elements and ``runs`` holds ``capacity``; call encode again with capacity=needed."""
+
+    def __init__(self, needed, capacity):
+        ValueError.__init__(self, 'MaskRuns: the run lengths need %d elements and runs holds %d; call encode again with capacity=%d'
+                            % (needed, capacity, needed))
+        self.needed, self.capacity = needed, capacity
+
+
+def default_run_capacity(sizes, K):
+    """Elements of ``runs`` when the caller names none: per frame K (8 w + 8) -- four boundary pairs per column and slot."""
+    return sum(k * (8 * w + 8) for (_, w), k in zip(sizes, K))
+
+
+class MaskRuns:
+    """What encode_frames coded: ``heads``, the (n, 16, 4) int64 tensor { count, offset, area, id } of include/frtm_hip.h, and ``runs``,
+    the concatenated run lengths (both on the device: coding does not synchronise), with ``sizes[i]`` = (h, w) and ``K[i]`` slots of frame i
+    and ``capacity``, the elements of ``runs`` the call could write.  ``runs`` is int32, not uint32 (torch's uint32 has no comparison,
+    indexing or fill kernels); every count is at most h w <= 2^28, so the bits are the same.  ``cpu()`` makes the copy of the heads (512
+    bytes per frame), then ONE copy of runs[:needed], and keeps both -- or raises RunsOverflow when needed > capacity; ``counts(i)`` and
+    ``rle(i)`` read that copy."""
+
+    def __init__(self, heads, runs, sizes, K, capacity):
+        if not isinstance(heads, torch.Tensor) or heads.dtype != torch.int64 or heads.dim() != 3 or tuple(heads.shape[1:]) != (OBJECT_SLOTS, RUNS_HEAD_WORDS):
+            raise TypeError('MaskRuns: heads is a (n, %d, %d) int64 tensor, got %s %s'
+                            % (OBJECT_SLOTS, RUNS_HEAD_WORDS, getattr(heads, 'dtype', type(heads).__name__), tuple(getattr(heads, 'shape', ()))))
+        if not isinstance(runs, torch.Tensor) or runs.dtype != torch.int32 or runs.dim() != 1:
+            raise TypeError('MaskRuns: runs is a 1-d int32 tensor, got %s %s' % (getattr(runs, 'dtype', type(runs).__name__), tuple(getattr(runs, 'shape', ()))))
+        sizes, K = [(int(h), int(w)) for h, w in sizes], [int(k) for k in K]
+        if len(K) != heads.shape[0] or len(sizes) != heads.shape[0] or any(not 1 <= k <= OBJECT_SLOTS for k in K):
+            raise ValueError('MaskRuns: %d frames, %d slot counts (1 .. %d), %d sizes' % (heads.shape[0], len(K), OBJECT_SLOTS, len(sizes)))
+        if not 1 <= int(capacity) <= runs.numel():
+            raise ValueError('MaskRuns: capacity %d of a runs of %d elements' % (capacity, runs.numel()))
+        self.heads, self.runs, self.sizes, self.K, self.capacity = heads, runs, sizes, K, int(capacity)
+        self._host = None
+
+    def __len__(self):
+        return self.heads.shape[0]
+
+    def cpu(self):
+        """-> (heads, runs[:needed]) on the host; two copies the first time, none after."""
+        if self._host is None or self._host[1] is None:
+            heads = self.heads.cpu() if self._host is None else self._host[0]
+            self._host = (heads, None)
+            count, offset = heads[-1, self.K[-1] - 1, :2].tolist()
+            if offset + count > self.capacity:
+                raise RunsOverflow(offset + count, self.capacity)
+            self._host = (heads, self.runs[:offset + count].cpu())
+        return self._host
+
+    def counts(self, i):
+        """-> {object id: the list of run lengths of the object's mask in frame i}."""
+        heads, runs = self.cpu()
+        return {oid: runs[offset:offset + count].tolist() for count, offset, _, oid in heads[i, :self.K[i]].tolist()}
+
+    def rle(self, i, compressed=False):
+        """-> {object id: {'size': [h, w], 'counts': list -- or bytes, COCO's string form, when ``compressed``}}."""
+        return {oid: {'size': list(self.sizes[i]), 'counts': rle_to_string(c) if compressed else c} for oid, c in self.counts(i).items()}
+
+
+def rle_to_string(counts):
+    """COCO's string form of a list of run lengths: from the fourth count on the difference to the count two before is coded; a value goes out
+    in 5-bit groups, low first, bit 0x20 marks 'more', and it is finished when the rest is 0 with bit 0x10 clear or -1 with bit 0x10 set;
+    every group + 48 is a character.  (A restatement of the coder of the COCO API, not a call into it.)"""
+    counts = [int(c) for c in counts]
+    out = bytearray()
+    for i, x in enumerate(counts):
+        if i > 2:
+            x -= counts[i - 2]
+        more = True
+        while more:
+            c = x & 0x1f
+            x >>= 5                                 # (arithmetic: a negative rest ends at -1)
+            more = x != -1 if c & 0x10 else x != 0
+            out.append((c | 0x20 if more else c) + 48)
+    return bytes(out)
+
+
+def rle_from_string(s):
+    """The list of run lengths of COCO's string form (rle_to_string's inverse)."""
+    s = bytes(s.encode('ascii') if isinstance(s, str) else s)
+    counts, p = [], 0
+    while p < len(s):
+        x, k, more = 0, 0, True
+        while more:
+            if p >= len(s):
+                raise ValueError('rle_from_string: the string ends inside a value')
+            c = s[p] - 48
+            if not 0 <= c < 64:
+                raise ValueError('rle_from_string: byte %d at %d is no character of the code' % (s[p], p))
+            x |= (c & 0x1f) << (5 * k)
+            more = bool(c & 0x20)
+            p, k = p + 1, k + 1
+            if not more and c & 0x10:
+                x |= -1 << (5 * k)
+        if len(counts) > 2:
+            x += counts[-2]
+        counts.append(x)
+    return counts
+
+
+def rle_decode(size, counts):
+    """The (h, w) numpy bool mask of a list of run lengths (or of its string form): runs of zeros and ones in turn, column-major."""
+    import numpy as np
+    h, w = (int(v) for v in size)
+    counts = rle_from_string(counts) if isinstance(counts, (bytes, str)) else [int(c) for c in counts]
+    if any(c < 0 for c in counts) or sum(counts) != h * w:
+        raise ValueError('rle_decode: the counts sum to %d, the size is %d x %d' % (sum(counts), h, w))
+    bits = np.zeros(len(counts), dtype=bool)
+    bits[1::2] = True
+    return np.repeat(bits, counts).reshape(w, h).T
+
+
+def encode_frames(answers, luts=None, ids=None, out=None, capacity=None):
+    """frtm_encode_frames: every object's mask of every frame as COCO run lengths (column-major, starting with a run of zeros), all frames in
+    FOUR launches on the current stream whatever their number, sizes and content; nothing synchronises.  ``answers``, ``luts``, ``ids``:
+    describe_frames's arguments and checks (the two calls share the uploaded table).  ``capacity``: the elements of ``runs``; default: the
+    sum over the frames of K (8 w + 8), or what ``out`` holds.  ``out``: a MaskRuns whose buffers (at least n x 16 x 4 words, and
+    ``capacity`` elements) are used again; only the first n x 16 x 4 words and min(needed, capacity) elements are written.  -> a MaskRuns;
+    its heads hold the true counts and offsets even when the lists did not fit (MaskRuns.cpu() then raises RunsOverflow with ``needed``).
+    The workspace comes from ops.workspace.  The format, exact in integers: include/frtm_hip.h."""
+    frames, device = _object_frames('encode_frames', answers, luts, ids)
+    n = len(frames)
+    Ks, sizes = [f[4] for f in frames], [(f[1], f[2]) for f in frames]
+    if capacity is not None and (isinstance(capacity, bool) or not isinstance(capacity, numbers.Integral) or not 1 <= capacity <= RUNS_MAX_CAPACITY):
+        raise ValueError('encode_frames: capacity is 1 .. 2^40 elements, got %r' % (capacity,))
+    need = n * OBJECT_SLOTS * RUNS_HEAD_WORDS
+    if out is None:
+        capacity = default_run_capacity(sizes, Ks) if capacity is None else int(capacity)
+        heads = torch.empty(n, OBJECT_SLOTS, RUNS_HEAD_WORDS, dtype=torch.int64, device=device)
+        runs = torch.empty(capacity, dtype=torch.int32, device=device)
+    else:
+        if not isinstance(out, MaskRuns):
+            raise TypeError('encode_frames: out is an ops.MaskRuns, got %s' % type(out).__name__)
+        heads, runs = out.heads, out.runs
+        if not heads.is_cuda or not runs.is_cuda:
+            raise RuntimeError('encode_frames: out is on %s; the kernel runs on the GPU only (no CPU fallback)' % (heads.device,))
+        if not heads.is_contiguous() or not runs.is_contiguous():
+            raise TypeError('encode_frames: out must be contiguous')
+        if heads.numel() < need:
+            raise ValueError('encode_frames: out holds %d head words, %d frames need %d' % (heads.numel(), n, need))
+        capacity = runs.numel() if capacity is None else int(capacity)
+        if capacity > runs.numel():
+            raise ValueError('encode_frames: capacity %d, out holds %d elements' % (capacity, runs.numel()))
+    kept = _object_table(frames, device)
+    L = H.lib()
+    work_bytes = L.frtm_encode_work_bytes(kept[0].data_ptr(), n, capacity)
+    if work_bytes == 0:
+        raise RuntimeError('frtm_encode_work_bytes failed: %s' % L.frtm_last_error().decode())
+    work = workspace(device, (work_bytes + 3) // 4)
+    H.call('frtm_encode_frames', kept[0].data_ptr(), H.ptr(kept[1]), n, H.ptr(heads), heads.numel(), H.ptr(runs), capacity, H.ptr(work),
+           work.numel() * work.element_size())
+    return MaskRuns(heads.view(-1)[:need].view(n, OBJECT_SLOTS, RUNS_HEAD_WORDS), runs, sizes, Ks, capacity)

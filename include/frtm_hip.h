@@ -911,6 +911,42 @@ int frtm_render_frames_u8(const long long* table_host, const long long* table_de
 int frtm_describe_frames(const long long* table_host, const long long* table_dev, int n, long long* out, size_t out_words,
                          frtm_stream_t stream);
 
+/* The tracked masks in the form consumers of segmentation read -- COCO run lengths, one list per object -- coded on the device
+ * (csrc/mask_runs.hip; ops.encode_frames, Tracker.encode, StreamPool.encode).  The conventions are frtm_describe_frames's: the table is passed
+ * twice (table_host is checked and sizes the grid and the workspace, table_dev is what the kernels read, and every workgroup checks its row
+ * again), rows carry ADDRESSES, everything is enqueued on `stream`, nothing synchronises and nothing is allocated.  The row is
+ * frtm_describe_frames's row word for word -- { form, h, w, answer, answer_bytes, K, ids, 0 }, the same forms and limits -- so a table built
+ * for one call serves the other, and the slot of a pixel is that call's slot (stack: the decoded plane; label map: the index of its id in ids,
+ * none when not listed).  Slot s of a frame is the binary mask b_s(y, x) = [slot(y, x) == s].
+ * The code of a slot.  With N = h w and p = x h + y (column-major, as COCO scans): the lengths of the maximal runs of equal bits of b_s(p),
+ * p = 0 .. N - 1, in order, STARTING WITH A RUN OF ZEROS: the first count is 0 when b_s(0) = 1.  With B the number of p in 1 .. N - 1 where
+ * b_s(p) != b_s(p - 1) the list has B + 1 + b_s(0) entries and they sum to N.  p - 1 of a pixel in row 0 is the last row of the previous
+ * column: a run continues from the bottom of a column into the top of the next.  All zeros: [N]; all ones: [0, N];
+ * h = 3, w = 4, rows 0110 / 0100 / 1101: [2, 5, 4, 1].
+ * heads: n x 16 x FRTM_RUNS_HEAD_WORDS 64-bit words, frame-major then slot (head_words, the words available, at least that many):
+ *   { count, offset, area, id }   count: the length of the slot's list; offset: where it starts in runs; area: the sum of its odd-indexed
+ *                                 counts (= word 0 of frtm_describe_frames); id: ids[s].  Slots s >= K: four zeros.
+ * The layout is fixed: offset(frame 0, slot 0) = 0 and every following (frame, slot) in use starts where the one before it ends; `needed` is
+ * offset + count of the last slot in use.  Element j of that concatenation is stored in runs[j] iff j < run_capacity: heads always holds the
+ * TRUE counts and offsets, a slot is complete iff offset + count <= run_capacity, and runs at or beyond min(needed, run_capacity) is not
+ * touched.  Every word of heads and every stored element is an exact function of the inputs: no atomics, no float arithmetic after the decode,
+ * no position that depends on an order of arrival; two calls give the same bytes.
+ * work: frtm_encode_work_bytes(table_host, n, run_capacity) bytes, 8-byte aligned; its content is this call's alone.  (That function runs on
+ * the host without a device; 0 and a message for a table, an n or a run_capacity that frtm_encode_frames would refuse.  The size is
+ * 4 (16 n + 2 n C) with C = max over the frames of K w ceil(h / 64): two words per (slot, column, 64-row segment).  run_capacity is checked but
+ * does not enter: the positions of the boundaries are never stored.)
+ * A call enqueues exactly FOUR operations on `stream`, whatever n, the sizes and the content: the kernel that counts every cell's boundaries,
+ * the scan of every slot's cells (which writes count, area and id), the scan of the slots (offsets and every list's last element), and the
+ * kernel that walks the pixels again and stores the run lengths.  Loads touch picture samples and the K id bytes only; stores touch heads,
+ * runs[0 .. min(needed, run_capacity)) and work only.
+ * Refused with FRTM_ERR_ARG and a message before anything is enqueued, outputs untouched: everything frtm_describe_frames refuses for its
+ * table, a null or misaligned heads / runs / work, head_words < n x 16 x 4, work_bytes below frtm_encode_work_bytes, run_capacity < 1 or
+ * > 2^40. */
+#define FRTM_RUNS_HEAD_WORDS 4
+size_t frtm_encode_work_bytes(const long long* table_host, int n, size_t run_capacity);
+int frtm_encode_frames(const long long* table_host, const long long* table_dev, int n, long long* heads, size_t head_words,
+                       unsigned int* runs, size_t run_capacity, void* work, size_t work_bytes, frtm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
