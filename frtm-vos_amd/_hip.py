@@ -167,6 +167,8 @@ SIGNATURES = {
     'frtm_describe_frames': (I, [P, P, I, P, ctypes.c_size_t, P]),
     'frtm_encode_work_bytes': (ctypes.c_size_t, [P, I, ctypes.c_size_t]),
     'frtm_encode_frames': (I, [P, P, I, P, ctypes.c_size_t, P, ctypes.c_size_t, P, ctypes.c_size_t, P]),
+    'frtm_clean_work_bytes': (ctypes.c_size_t, [P, I]),
+    'frtm_clean_frames': (I, [P, P, I, I, ctypes.c_longlong, I, I, P, ctypes.c_size_t, P, ctypes.c_size_t, P]),
 }
 
 _lib = None

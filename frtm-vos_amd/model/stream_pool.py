@@ -151,6 +151,7 @@ class StreamPool:
         self._native_planes = {}
         self.describe_launches = 0      # ops.describe_frames launches made by describe() so far: one per call (diagnostics)
         self.encode_launches = 0        # ops.encode_frames launches made by encode() so far: one per call (diagnostics)
+        self.clean_launches = 0         # ops.clean_frames calls made by clean() so far: one per call (diagnostics)
 
     # ---- streams ------------------------------------------------------------------------------------------------------------
     def open(self):
@@ -315,6 +316,20 @@ class StreamPool:
         coded = ops.encode_frames(stacks, luts=luts, out=out, capacity=capacity)
         self.encode_launches += 1
         return {sid: i for i, sid in enumerate(sids)}, coded
+
+    @torch.no_grad()
+    def clean(self, sids=None, out=None, **rule):
+        """The last answer of every stream named cleaned on the device -- every object split into its connected parts, specks dropped by
+        ``rule`` (connectivity, min_area, largest_only, fill, components) --: -> ({sid: index}, ops.CleanedAnswers), ONE ops.clean_frames
+        call for all of them whatever their sizes and object counts.  ``sids`` and the stack every stream is cleaned from: describe()'s.
+        A post-process of the answers: no stream's ``current_masks``, memory or label map is written.  ``out``: a CleanedAnswers whose
+        buffers are used again."""
+        sids, stacks, luts = self._answers('clean', sids)
+        plane_ids = [(0,) + tuple(int(t.object_id) for t in sorted(self._streams[sid].tracker.targets.values(), key=lambda t: t.index))
+                     for sid in sids]
+        cleaned = ops.clean_frames(stacks, luts=luts, plane_ids=plane_ids, out=out, **rule)
+        self.clean_launches += 1
+        return {sid: i for i, sid in enumerate(sids)}, cleaned
 
     def _resize_batch(self, tb, natives, frames, batch):
         """The tick's frames, of any sizes, into ``batch`` (B,3,h,w) at the working size: copied into ONE packed staging buffer (16-byte

@@ -1176,6 +1176,17 @@ class Tracker(nn.Module):
         stack, lut = self.describe_answer(self.native_labels)
         return ops.encode_frames([stack], luts=[lut], out=out, capacity=capacity)
 
+    @torch.no_grad()
+    def clean(self, out=None, **rule):
+        """The last answer of track() cleaned on the device (ops.clean_frames on the stack track() returned -- under ``working_size`` the
+        native-size stack -- and the object LUT): every object split into its connected parts and the rule applied; ``rule``:
+        connectivity, min_area, largest_only, fill, components.  -> an ops.CleanedAnswers of one frame whose ``answers()`` go to
+        ops.describe_frames / encode_frames / render_frames.  A post-process of the ANSWER: ``current_masks``, the target models' memory
+        and every other state of the tracker stay as they are.  ``out``: a CleanedAnswers whose buffers are used again."""
+        stack, lut = self.describe_answer(self.native_labels)
+        plane_ids = (0,) + tuple(int(t.object_id) for t in sorted(self.targets.values(), key=lambda t: t.index))
+        return ops.clean_frames([stack], luts=[lut], plane_ids=[plane_ids], out=out, **rule)
+
     def _track(self, image, features, im_size):
         if self._unchecked_fits and not self._in_run_sequence:
             self._check_first_frame_fits()

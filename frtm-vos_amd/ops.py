@@ -1566,3 +1566,183 @@ def encode_frames(answers, luts=None, ids=None, out=None, capacity=None):
     H.call('frtm_encode_frames', kept[0].data_ptr(), H.ptr(kept[1]), n, H.ptr(heads), heads.numel(), H.ptr(runs), capacity, H.ptr(work),
            work.numel() * work.element_size())
     return MaskRuns(heads.view(-1)[:need].view(n, OBJECT_SLOTS, RUNS_HEAD_WORDS), runs, sizes, Ks, capacity)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# The answer cleaned on the device: connected parts, specks dropped (csrc/object_parts.hip)
+# ----------------------------------------------------------------------------------------------------------------------
+PARTS_ROW_WORDS = 16                                # FRTM_PARTS_ROW_WORDS
+PARTS_WORDS = 12                                    # FRTM_PARTS_WORDS
+PARTS_TILE_H = 32                                   # FRTM_PARTS_TILE_H
+PARTS_TILE_W = 64                                   # FRTM_PARTS_TILE_W: the tile of the local pass; its sides are the seams
+PARTS_MAX_MIN_AREA = 1 << 28
+PARTS_TABLES_KEPT = 256                             # uploaded row tables clean_frames keeps, least recently used first out
+_parts_tables = collections.OrderedDict()
+
+PartStats = collections.namedtuple('PartStats', 'parts kept area kept_area largest_area largest_box largest_name ruled')
+PartStats.__doc__ = """One object of one frame (CleanedAnswers.objects): ``parts`` connected parts, ``kept`` of them kept; ``area`` pixels,
+``kept_area`` of them kept; ``largest_area``, ``largest_box`` (x_min, y_min, x_max, y_max), inclusive, and ``largest_name`` (the smallest
+y w + x among its pixels) of the largest part, ties to the smaller name -- box and name None when the object has no pixel; ``ruled`` False
+when the object's id is ``fill`` (the background: counted, all kept)."""
+
+
+def clean_work_bytes(h, w):
+    """A frame's part of clean_frames's work buffer: 16 packed words, then two int32 per pixel, a multiple of 16 bytes
+    (frtm_clean_work_bytes is the sum over the frames)."""
+    return (128 + 8 * h * w + 15) // 16 * 16
+
+
+class CleanedAnswers:
+    """What clean_frames made: ``labels[i]``, the (h, w) uint8 cleaned label map of frame i (a view of one packed buffer, every frame on a
+    16-byte boundary); ``components[i]``, the (h, w) int32 map of part names (-1: no slot), or None when not asked for; ``words``, the
+    (n, 16, 12) int64 tensor of include/frtm_hip.h; ``status``, n int64 words behind it -- all on the device: cleaning does not
+    synchronise.  ``cpu()`` makes ONE device-to-host copy of words and status and keeps it; it raises RuntimeError naming the frame whose
+    status is not 0.  ``objects(i)`` -> {object id: PartStats}; ``ids(i)``: the ids to pass on with ``labels[i]``; ``answers()`` ->
+    (labels, ids) for describe_frames / encode_frames / render_frames."""
+
+    def __init__(self, label_buf, comp_buf, word_buf, sizes, K, ids):
+        sizes, K = [(int(h), int(w)) for h, w in sizes], [int(k) for k in K]
+        n = len(sizes)
+        if len(K) != n or len(ids) != n or n < 1 or any(not 1 <= k <= OBJECT_SLOTS for k in K):
+            raise ValueError('CleanedAnswers: %d sizes, %d slot counts (1 .. %d), %d id lists' % (n, len(K), OBJECT_SLOTS, len(ids)))
+        if not isinstance(word_buf, torch.Tensor) or word_buf.dtype != torch.int64 or word_buf.dim() != 1 or word_buf.numel() < n * (OBJECT_SLOTS * PARTS_WORDS + 1):
+            raise TypeError('CleanedAnswers: the words are a 1-d int64 tensor of at least %d x (%d x %d + 1) elements, got %s %s'
+                            % (n, OBJECT_SLOTS, PARTS_WORDS, getattr(word_buf, 'dtype', type(word_buf).__name__), tuple(getattr(word_buf, 'shape', ()))))
+        if not isinstance(label_buf, torch.Tensor) or label_buf.dtype != torch.uint8 or label_buf.dim() != 1:
+            raise TypeError('CleanedAnswers: the label maps are a 1-d uint8 tensor, got %s' % getattr(label_buf, 'dtype', type(label_buf).__name__))
+        if comp_buf is not None and (not isinstance(comp_buf, torch.Tensor) or comp_buf.dtype != torch.int32 or comp_buf.dim() != 1):
+            raise TypeError('CleanedAnswers: the component maps are a 1-d int32 tensor or None, got %s' % getattr(comp_buf, 'dtype', type(comp_buf).__name__))
+        offs, o = [], 0
+        for h, w in sizes:
+            offs.append(o)
+            o += (h * w + 15) // 16 * 16
+        if label_buf.numel() < o or (comp_buf is not None and comp_buf.numel() < o):
+            raise ValueError('CleanedAnswers: the frames need %d packed pixels, the buffers hold %d and %s'
+                             % (o, label_buf.numel(), None if comp_buf is None else comp_buf.numel()))
+        self.label_buf, self.comp_buf, self.word_buf = label_buf, comp_buf, word_buf
+        self.sizes, self.K, self.offsets, self.pixels = sizes, K, offs, o
+        self._ids = [None if v is None else tuple(int(x) for x in v) for v in ids]
+        nw = n * OBJECT_SLOTS * PARTS_WORDS
+        self.words = word_buf[:nw].view(n, OBJECT_SLOTS, PARTS_WORDS)
+        self.status = word_buf[nw:nw + n]
+        self.labels = [label_buf[a:a + h * w].view(h, w) for a, (h, w) in zip(offs, sizes)]
+        self.components = [None if comp_buf is None else comp_buf[a:a + h * w].view(h, w) for a, (h, w) in zip(offs, sizes)]
+        self._host = None
+
+    def __len__(self):
+        return len(self.sizes)
+
+    def cpu(self):
+        """-> (words, status) on the host; one copy the first time, none after.  RuntimeError when a frame's status is not 0."""
+        if self._host is None:
+            n = len(self)
+            nw = n * OBJECT_SLOTS * PARTS_WORDS
+            host = self.word_buf[:nw + n].cpu()
+            self._host = (host[:nw].view(n, OBJECT_SLOTS, PARTS_WORDS), host[nw:])
+        bad = [(i, s) for i, s in enumerate(self._host[1].tolist()) if s != 0]
+        if bad:
+            raise RuntimeError('CleanedAnswers: frame %d has status %d: a bounded loop of the labelling gave up (1 local, 2 seam, 4 flatten); '
+                               'its outputs are not valid' % bad[0])
+        return self._host
+
+    def objects(self, i):
+        out = {}
+        for parts, kept, area, kept_area, big, name, x0, y0, x1, y1, ruled, oid in self.cpu()[0][i, :self.K[i]].tolist():
+            out[oid] = PartStats(parts, kept, area, kept_area, big, (x0, y0, x1, y1) if area else None, name if area else None, bool(ruled))
+        return out
+
+    def ids(self, i):
+        """The ids that go with ``labels[i]``: what the caller listed (a label map's ids, a stack's plane_ids) -- no copy --, else word 11
+        of the frame's slots from cpu()."""
+        if self._ids[i] is None:
+            self._ids[i] = tuple(self.cpu()[0][i, :self.K[i], 11].tolist())
+        return self._ids[i]
+
+    def answers(self):
+        """-> (labels, ids): ``ops.describe_frames(labels, ids=ids)``, ``ops.encode_frames(labels, ids=ids)``."""
+        return list(self.labels), [self.ids(i) for i in range(len(self))]
+
+
+def _parts_rule(who, connectivity, min_area, largest_only, fill):
+    for name, v in (('connectivity', connectivity), ('min_area', min_area), ('fill', fill)):
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+            raise TypeError('%s: %s is an int, got %r' % (who, name, v))
+    if connectivity not in (4, 8):
+        raise ValueError('%s: connectivity is 4 or 8, got %r' % (who, connectivity))
+    if not 1 <= min_area <= PARTS_MAX_MIN_AREA:
+        raise ValueError('%s: min_area is 1 .. 2^28, got %r' % (who, min_area))
+    if not isinstance(largest_only, (bool, numbers.Integral)) or largest_only not in (0, 1):
+        raise ValueError('%s: largest_only is a bool, got %r' % (who, largest_only))
+    if not 0 <= fill <= 255:
+        raise ValueError('%s: fill is 0 .. 255, got %r' % (who, fill))
+    return int(connectivity), int(min_area), int(bool(largest_only)), int(fill)
+
+
+def clean_frames(answers, luts=None, ids=None, connectivity=8, min_area=1, largest_only=False, fill=0, components=False, plane_ids=None,
+                 out=None):
+    """frtm_clean_frames: every object of every frame split into its connected parts (``connectivity`` 4 or 8), the parts measured, and a
+    cleaned uint8 label map written per frame, all frames in SIX launches on the current stream whatever their number, sizes and content;
+    nothing synchronises.  ``answers``, ``luts``, ``ids``: describe_frames's arguments and checks.  The rule: an object whose id is not
+    ``fill`` keeps the parts of at least ``min_area`` pixels -- with ``largest_only`` only its largest part, ties to the part that starts
+    first --; every other pixel of it becomes ``fill``; the object whose id is ``fill`` (the background) is counted and left as it is.
+    ``components``: also write the int32 map of part names.  ``plane_ids[i]``: the ids of a stack's planes when the caller knows them on the
+    host (then CleanedAnswers.ids needs no copy).  ``out``: a CleanedAnswers whose buffers are used again when they are large enough;
+    only the frames' own pixels and words are written.  -> a CleanedAnswers.  The workspace comes from ops.workspace.  The parts, the rule
+    and the words, exact in integers: include/frtm_hip.h.  Not done here: filling holes, giving removed pixels a neighbour's label,
+    opening or closing, feeding the map back into the tracker, a confidence for the cleaned map."""
+    who = 'clean_frames'
+    frames, device = _object_frames(who, answers, luts, ids)
+    n = len(frames)
+    connectivity, min_area, largest_only, fill = _parts_rule(who, connectivity, min_area, largest_only, fill)
+    if plane_ids is not None and len(plane_ids) != n:
+        raise ValueError('%s: %d answers, %d plane_ids' % (who, n, len(plane_ids)))
+    Ks, sizes = [f[4] for f in frames], [(f[1], f[2]) for f in frames]
+    host_ids = []
+    for i, (stack, _, _, _, K, which) in enumerate(frames):
+        known = which if not stack else None if plane_ids is None or plane_ids[i] is None else _object_ids(i, plane_ids[i], who)
+        if known is not None and len(known) != K:
+            raise ValueError('%s: plane_ids[%d] lists %d ids, the stack has %d planes' % (who, i, len(known), K))
+        host_ids.append(known)
+    pixels = sum((h * w + 15) // 16 * 16 for h, w in sizes)
+    n_words = n * (OBJECT_SLOTS * PARTS_WORDS + 1)
+    if out is None:
+        label_buf = torch.empty(pixels, dtype=torch.uint8, device=device)
+        comp_buf = torch.empty(pixels, dtype=torch.int32, device=device) if components else None
+        word_buf = torch.empty(n_words, dtype=torch.int64, device=device)
+    else:
+        if not isinstance(out, CleanedAnswers):
+            raise TypeError('%s: out is an ops.CleanedAnswers, got %s' % (who, type(out).__name__))
+        label_buf, comp_buf, word_buf = out.label_buf, out.comp_buf if components else None, out.word_buf
+        if not label_buf.is_cuda or not word_buf.is_cuda or (comp_buf is not None and not comp_buf.is_cuda):
+            raise RuntimeError('%s: out is on %s; the kernels run on the GPU only (no CPU fallback)' % (who, label_buf.device))
+        if components and comp_buf is None:
+            raise ValueError('%s: components asked for, out holds no component maps' % who)
+        if label_buf.numel() < pixels or word_buf.numel() < n_words or (comp_buf is not None and comp_buf.numel() < pixels):
+            raise ValueError('%s: out holds %d pixels and %d words, %d frames need %d and %d' % (who, label_buf.numel(), word_buf.numel(), n, pixels, n_words))
+    kept = _object_table(frames, device)
+    L = H.lib()
+    first = torch.zeros(n, PARTS_ROW_WORDS, dtype=torch.int64)
+    first[:, :OBJECT_ROW_WORDS] = kept[0]
+    work_bytes = L.frtm_clean_work_bytes(first.data_ptr(), n)
+    if work_bytes == 0:
+        raise RuntimeError('frtm_clean_work_bytes failed: %s' % L.frtm_last_error().decode())
+    work = workspace(device, (work_bytes + 15) // 4 + 4)
+    base = (H.ptr(work) + 15) // 16 * 16
+    key = (device.index, H.ptr(label_buf), None if comp_buf is None else H.ptr(comp_buf), base) + tuple(tuple(r) for r in kept[0].tolist())
+    table = _parts_tables.get(key)
+    if table is None:
+        o = wo = 0
+        for i, (h, w) in enumerate(sizes):
+            first[i, OBJECT_ROW_WORDS:] = torch.tensor([H.ptr(label_buf) + o, h * w, 0 if comp_buf is None else H.ptr(comp_buf) + 4 * o,
+                                                        0 if comp_buf is None else 4 * h * w, base + wo, clean_work_bytes(h, w), 0, 0], dtype=torch.int64)
+            o += (h * w + 15) // 16 * 16
+            wo += clean_work_bytes(h, w)
+        table = _parts_tables[key] = (first, H.upload(first, device), kept)
+        if len(_parts_tables) > PARTS_TABLES_KEPT:
+            _parts_tables.popitem(last=False)
+    else:
+        _parts_tables.move_to_end(key)
+    nw = n * OBJECT_SLOTS * PARTS_WORDS
+    H.call('frtm_clean_frames', table[0].data_ptr(), H.ptr(table[1]), n, connectivity, min_area, largest_only, fill, H.ptr(word_buf), nw,
+           H.ptr(word_buf) + 8 * nw, n)
+    return CleanedAnswers(label_buf, comp_buf, word_buf, sizes, Ks, host_ids)

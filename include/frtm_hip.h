@@ -947,6 +947,59 @@ size_t frtm_encode_work_bytes(const long long* table_host, int n, size_t run_cap
 int frtm_encode_frames(const long long* table_host, const long long* table_dev, int n, long long* heads, size_t head_words,
                        unsigned int* runs, size_t run_capacity, void* work, size_t work_bytes, frtm_stream_t stream);
 
+/* The answer cleaned on the device (csrc/object_parts.hip; ops.clean_frames, Tracker.clean, StreamPool.clean): every object of n frames of any
+ * sizes, label maps and mask stacks mixed, split into its connected parts, the parts measured, a keep rule applied and a cleaned uint8 label
+ * map written per frame -- an answer frtm_render_frames_u8, frtm_describe_frames and frtm_encode_frames accept as it is.  The conventions are
+ * frtm_describe_frames's: the table is passed twice (table_host is checked and sizes the grid, table_dev is what the kernels read, and every
+ * workgroup checks its row again), rows carry ADDRESSES, everything is enqueued on `stream`, nothing synchronises and nothing is allocated.
+ * A row is FRTM_PARTS_ROW_WORDS 64-bit words:
+ *   { form, h, w, answer, answer_bytes, K, ids, 0,   labels, labels_bytes, components, components_bytes, work, work_bytes, 0, 0 }
+ * The first 8 words are frtm_describe_frames's row word for word, with its forms, limits and check.  labels: the h x w uint8 cleaned map
+ * (labels_bytes >= h w available; it may not overlap the answer); components: 0 for none, or a 4-byte aligned h x w int32 map
+ * (components_bytes >= 4 h w); work: this frame's part of the work buffer, 16-byte aligned, work_bytes >= 16 ceil((128 + 8 h w) / 16): 16 packed
+ * 64-bit words (a slot's largest part), then two int32 per pixel -- the parent (finally: the name) and the area at the root.
+ * frtm_clean_work_bytes(table_host, n) is the sum of that over the frames, so the parts laid out one behind the other fit; it reads the first
+ * 8 words of every row only, runs on the host without a device, and returns 0 and a message for a table or an n frtm_clean_frames would refuse.
+ * The slot of a pixel is frtm_describe_frames's slot (stack: the decoded plane, a NaN never wins, threshold 0.5; label map: the index of its
+ * id in ids, none when not listed).  The rule, per call: connectivity 4 or 8; min_area 1 .. 2^28; largest_only 0 or 1; fill 0 .. 255.
+ * Parts.  A part is a maximal set of pixels of one slot joined by 4- (or 8-) neighbour steps inside the picture; its NAME is the smallest
+ * y w + x among its pixels; pixels without a slot belong to no part.  Slot s is RULED when ids[s] != fill.  A part of a ruled slot is kept iff
+ * its area >= min_area and (largest_only is 0 or it is its slot's largest part, ties to the smaller name); the parts of an unruled slot (the
+ * background) are all kept, and counted all the same.
+ * Outputs.  labels: ids[slot] where the pixel's part is kept, else fill; a label-map pixel without a slot keeps its input byte.  components:
+ * the name of the pixel's part, -1 without a slot.  words: n x 16 x FRTM_PARTS_WORDS 64-bit words, frame-major then slot (word_count, the
+ * words available, at least that many); slot s < K (slots s >= K: twelve zeros):
+ *   0  parts         parts of the slot                  1  kept       parts kept
+ *   2  area          pixels of the slot (= word 0 of frtm_describe_frames)      3  kept_area  pixels kept
+ *   4  largest_area  area of the largest part           5  largest_name   its name; -1 for an empty slot
+ *   6 .. 9  x_min, y_min, x_max, y_max of the largest part, inclusive; of an empty slot w, h, -1, -1
+ *   10 ruled  0 or 1                                    11 id         ids[s]
+ * status: n 64-bit words (status_count at least n): 0, or the bits of the phases in which a bounded loop reached its cap (1 local, 2 seam,
+ * 4 flatten) -- by the bounds in object_parts.hip that cannot happen; a frame with a non-zero status has unspecified outputs.
+ * All accumulation is in integers and no output depends on an order of arrival: the root of a part is its smallest pixel whatever the order
+ * of the unions, areas are integer sums, and the largest part is ONE 64-bit unsigned maximum over area << 32 | (2^31 - 1 - name).  Two calls
+ * give the same bytes.  A call enqueues exactly SIX operations on `stream`, whatever n, the sizes and the content:
+ *   begin    the start of every word (zeros, the empty box, ruled, id), status and the packed words
+ *   local    per FRTM_PARTS_TILE_H x FRTM_PARTS_TILE_W tile: the slots decoded (kept in labels for the later passes), row runs from ballots,
+ *            union-find in LDS; parent[p] = the tile's smallest pixel of p's part, area = the part's pixels in the tile (at that pixel)
+ *   seam     every pixel on a tile seam joined with its neighbours across the seam: lock-free unions, agent-scope atomics only
+ *   flatten  parent[p] = the root; the tile-local areas added to the root's
+ *   slots    parts, area and the packed maximum per slot, reduced per workgroup, one integer atomic per workgroup and word
+ *   write    labels, components, kept, kept_area and the largest part's box, reduced per workgroup likewise
+ * No grid barrier, no flag a workgroup waits on, no loop that runs until convergence.  Loads touch picture samples, the K id bytes, labels
+ * and work; stores touch labels, components (when given), work, words and status only.
+ * Refused with FRTM_ERR_ARG and a message before anything is enqueued, outputs untouched: everything frtm_describe_frames refuses for the
+ * first 8 words, a null, misaligned or too small labels / components / work / words / status, labels overlapping the answer, non-zero last
+ * words, n outside 1 .. 65535, connectivity other than 4 or 8, min_area outside 1 .. 2^28, largest_only other than 0 or 1, fill outside
+ * 0 .. 255. */
+#define FRTM_PARTS_ROW_WORDS 16
+#define FRTM_PARTS_WORDS 12
+#define FRTM_PARTS_TILE_H 32
+#define FRTM_PARTS_TILE_W 64
+size_t frtm_clean_work_bytes(const long long* table_host, int n);
+int frtm_clean_frames(const long long* table_host, const long long* table_dev, int n, int connectivity, long long min_area, int largest_only,
+                      int fill, long long* words, size_t word_count, long long* status, size_t status_count, frtm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
