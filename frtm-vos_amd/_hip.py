@@ -155,6 +155,7 @@ SIGNATURES = {
     'frtm_adam_amsgrad': (I, [P, I, P, I, D, D, D, D, D, D, D, I, P]),
     'frtm_resize_frames_u8': (I, [P, ctypes.c_size_t, P, P, I, I, P, I, I, P]),
     'frtm_target_apply_grouped': (I, [P, ctypes.c_size_t, I, P, P, P, I, I, I, I, I, P, P, P]),
+    'frtm_target_apply_grouped_tiles': (I, [I, I, I, I, ctypes.POINTER(I), ctypes.POINTER(I)]),
     'frtm_resize_labels_u8': (I, [P, ctypes.c_size_t, P, P, I, P, I, I, P]),
     'frtm_tse_inject_indexed': (I, [P, P, P, P, I, P, I, I, I, I, I, I, P, P]),
     'frtm_cab_gate_indexed': (I, [P, P, P, I, P, P, P, P, I, I, P, P]),

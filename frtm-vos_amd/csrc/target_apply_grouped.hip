@@ -128,11 +128,15 @@ __global__ __launch_bounds__(GP_NT) void k_grouped_project(const float* __restri
 // tables: each lane walks its channels in ascending order, 9 taps each; the 4 channel groups of a wave are added by a butterfly
 // and the 4 waves as (0 + 1) + (2 + 3).  One form for every G: a pair's scores do not depend on the launch they are part of.
 constexpr int GS_PX = 16;
-__global__ __launch_bounds__(256) void k_grouped_scores(const float* __restrict__ cft, const float* const* __restrict__ w2_tab, int C, int h, int w,
+__global__ __launch_bounds__(256) void k_grouped_scores(const float* __restrict__ cft, int F, const int* __restrict__ frame_of_pair,
+                                                         const float* const* __restrict__ w2_tab, int C, int h, int w,
                                                          float* __restrict__ scores) {
   constexpr int CGW = 64 / GS_PX, NG = 4 * CGW;
   __shared__ float red[4][GS_PX];
   const int pair = blockIdx.y, lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  // (uniform per workgroup, before the barrier) the projection wrote no features for a pair that names no frame of the batch: cft[pair]
+  // holds whatever the workspace held, so neither read it nor write scores[pair]
+  if ((unsigned)frame_of_pair[pair] >= (unsigned)F) return;
   const int pl = lane % GS_PX, cg = wid * CGW + lane / GS_PX;
   const int hw = h * w;
   const int px_ = blockIdx.x * GS_PX + pl;
@@ -177,6 +181,18 @@ static void launch_project(int FN, dim3 grid, hipStream_t st, const float* feats
   else k_grouped_project<FM, 2><<<grid, GP_NT, 0, st>>>(feats, pitch, F, fop, w1T, Cin, c, hw, cft);
 }
 
+// The one definition of the projection's tile: FM = 16-row MFMA blocks per wave row (2 * FM * 16 >= c rows), FN = 1 or 2 column blocks per
+// wave column.  64-column tiles (FN = 2) read each pair's features once and fill the 256 CUs from G = 10 at 30x54; below a chip's worth of
+// those, 32-column tiles (twice the workgroups).  Same chain per output element either way.
+int frtm_target_apply_grouped_tiles(int G, int c, int h, int w, int* fm, int* fn) {
+  FRTM_CHECK_ARG(G >= 1 && G <= 65535 && h >= 1 && w >= 1 && (long long)h * w <= (1 << 24) && c >= 1 && c <= 128 && fm && fn,
+                 "frtm_target_apply_grouped_tiles: needs 1 <= G <= 65535, 1 <= c <= 128, a non-empty map of at most 2^24 pixels (got G=%d c=%d %dx%d)",
+                 G, c, h, w);
+  *fm = ceil_div(c, 32);
+  *fn = ((long long)ceil_div(h * w, 64) * G >= 256) ? 2 : 1;
+  return FRTM_OK;
+}
+
 int frtm_target_apply_grouped(const float* feats, size_t frame_pitch, int F, const int* frame_of_pair, const float* const* w1T,
                               const float* const* w2, int G, int Cin, int c, int h, int w, float* cft, float* scores, frtm_stream_t stream) {
   FRTM_CHECK_ARG(feats && frame_of_pair && w1T && w2 && cft && scores, "frtm_target_apply_grouped: null argument");
@@ -187,11 +203,9 @@ int frtm_target_apply_grouped(const float* feats, size_t frame_pitch, int F, con
                  "frtm_target_apply_grouped: map %dx%d x %d channels too large, or frame pitch %zu below Cin*h*w", h, w, Cin, frame_pitch);
   hipStream_t st = (hipStream_t)stream;
   const int hw = h * w;
-  // 64-column tiles read each pair's features once and fill the 256 CUs from G = 10 at 30x54; below a chip's worth of those, 32-column
-  // tiles (twice the workgroups).  Same chain per output element either way.
-  const int FN = ((long long)ceil_div(hw, 64) * G >= 256) ? 2 : 1;
+  int FM, FN;
+  if (frtm_target_apply_grouped_tiles(G, c, h, w, &FM, &FN) != FRTM_OK) return FRTM_ERR_ARG;
   dim3 grid(ceil_div(hw, FN * 32), 1, G);
-  const int FM = ceil_div(c, 32);
   switch (FM) {
     case 1: launch_project<1>(FN, grid, st, feats, frame_pitch, F, frame_of_pair, w1T, Cin, c, hw, cft); break;
     case 2: launch_project<2>(FN, grid, st, feats, frame_pitch, F, frame_of_pair, w1T, Cin, c, hw, cft); break;
@@ -200,7 +214,7 @@ int frtm_target_apply_grouped(const float* feats, size_t frame_pitch, int F, con
   }
   FRTM_LAUNCH_CHECK();
   dim3 g2(ceil_div(hw, GS_PX), G);
-  k_grouped_scores<<<g2, 256, 0, st>>>(cft, w2, c, h, w, scores);
+  k_grouped_scores<<<g2, 256, 0, st>>>(cft, F, frame_of_pair, w2, c, h, w, scores);
   FRTM_LAUNCH_CHECK();
   return FRTM_OK;
 }

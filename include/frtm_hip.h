@@ -516,7 +516,8 @@ int frtm_filter_scores_pitched(const float* X, const float* f, int N, int C, int
 /* Grouped target-model scoring (csrc/target_apply_grouped.hip): for G (frame, target) pairs, what G calls of frtm_conv2d (1x1 projection)
  * + frtm_filter_scores on one frame each compute, in two launches.
  *   feats          base of a feature batch (F, Cin, h, w); frame_pitch floats between frames (>= Cin*h*w: the frames need not be dense)
- *   frame_of_pair  device int32[G]: the frame pair p reads; several pairs may name one frame (a pair naming none of the F frames is skipped)
+ *   frame_of_pair  device int32[G]: the frame pair p reads; several pairs may name one frame (a pair naming none of the F frames is skipped:
+ *                  its slices of cft and of scores are left untouched)
  *   w1T, w2        device tables of G pointers: projection in GEMM layout [Cin][c]; filter (1, c, 3, 3)
  *   cft            (G, c, h, w) dense: pair p's projected features;   scores (G, 1, h, w) dense, in pair order
  * Projection on fp32 MFMA, no split-K, no atomics: every element is one chain over K = Cin in ascending order; the 3x3 pass (zero
@@ -524,6 +525,11 @@ int frtm_filter_scores_pitched(const float* X, const float* f, int N, int C, int
  * Any h, w; c <= 128; Cin a multiple of 32; everything else fails with FRTM_ERR_ARG. */
 int frtm_target_apply_grouped(const float* feats, size_t frame_pitch, int F, const int* frame_of_pair, const float* const* w1T,
                               const float* const* w2, int G, int Cin, int c, int h, int w, float* cft, float* scores, frtm_stream_t stream);
+/* The tile form frtm_target_apply_grouped projects G pairs of c channels on an h x w map with: *fm = ceil(c / 32) in 1..4 (a tile holds
+ * 32 * fm rows, all c channels), *fn = 2 (64-pixel tiles) when ceil(h*w / 64) * G >= 256, else 1 (32-pixel tiles).  Host only, no launch:
+ * the launcher itself calls it, and so do the tests to know which of the eight compiled forms a shape runs.  FRTM_ERR_ARG outside
+ * 1 <= G <= 65535, 1 <= c <= 128, 1 <= h*w <= 2^24. */
+int frtm_target_apply_grouped_tiles(int G, int c, int h, int w, int* fm, int* fn);
 /* count[k] = #pixels with masks[k] > 0.5   (the early-out test of discriminator.py:214), int32[n] */
 int frtm_count_above(const float* masks, int n, int HW, float thr, int* count, frtm_stream_t stream);
 

@@ -8,7 +8,8 @@ gamma(n) = n u / (1 - n u), u = 2^-24 (Higham, Accuracy and Stability of Numeric
     |s - s64|     <= gamma(9c + 1) * (|f| conv |cft|)  +  |f| conv (gamma(Cin + 1) * |W|^T |X|)
 
 the second line being the rounding of the 3x3 pass over the features the kernel really read plus the projection's own error carried
-through the filter.  A mixed-up pair, frame or table entry misses these bounds by orders of magnitude (the data is O(1), the bounds 1e-5).
+through the filter (both bounds: tests/_grouped_refs.py, shared with tests/test_grouped_scoring_gpu.py, which runs the kernels' other tile
+forms and edges).  A mixed-up pair, frame or table entry misses these bounds by orders of magnitude (the data is O(1), the bounds 1e-5).
 Pairs do not interact, so a pair's result must be BITWISE the same alone, inside a larger launch and with the tables reversed.
 
 Pool level: four streams against one fresh Tracker per stream running the reference's literal loop, with the gates of
@@ -17,16 +18,12 @@ import types
 
 import pytest
 import torch
-import torch.nn.functional as F
+
+from _grouped_refs import _bounds, _worst
 
 pytestmark = [pytest.mark.gpu, pytest.mark.timeout(600)]
 
 DEV = 'cuda'
-U = 2.0 ** -24
-
-
-def gamma(n):
-    return n * U / (1 - n * U)
 
 
 # (Cin, c, h, w, frames, frame_of_pair, extra floats between frames)
@@ -60,23 +57,6 @@ def _run(case, pairs):
     torch.cuda.synchronize()
     assert tuple(cft.shape) == (len(pairs), case.c, case.h, case.w) and tuple(s.shape) == (len(pairs), 1, case.h, case.w)
     return cft.cpu(), s.cpu()
-
-
-def _bounds(Cin, c, X, w1T, w2, cft):
-    """fp64 results and the two bounds of the module docstring for ONE pair: X (Cin,h,w), w1T (Cin,c), w2 (1,c,3,3), cft the kernel's."""
-    h, w = X.shape[-2:]
-    X64, W64, f64 = X.double().reshape(Cin, h * w), w1T.double(), w2.double()
-    cft64 = (W64.t() @ X64).reshape(1, c, h, w)
-    b1 = gamma(Cin + 1) * (W64.abs().t() @ X64.abs()).reshape(1, c, h, w)
-    s64 = F.conv2d(cft64, f64, padding=1)
-    b2 = gamma(9 * c + 1) * F.conv2d(cft.double().abs().reshape(1, c, h, w), f64.abs(), padding=1) + F.conv2d(b1, f64.abs(), padding=1)
-    return cft64, b1, s64, b2
-
-
-def _worst(got, ref, bound):
-    err = (got.double().reshape(ref.shape) - ref).abs()
-    assert bool((err[bound == 0] == 0).all())
-    return float((err / bound.clamp(min=1e-300)).max())
 
 
 @pytest.mark.parametrize('name', list(CASES))
